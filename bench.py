@@ -12,10 +12,19 @@ Headline workload (BASELINE.json config 2): TSP-100, B = 65,536 instances per GP
 the fused one-launch episode kernel ``co_tsp_rollout``.
 ``value`` = world * B * 100 * K / (max over ranks of the timed wall time).
 
-Also reported (``modes``): the same episode stepwise (one launch per env step,
-TensorDict state in HBM between steps, HIP graph), the in-kernel nearest-unvisited
-policy, and SLAP (examples/slap.py instance, B = 16,384).  ``cpu_baseline`` is the
-CPU oracle (plain-PyTorch restatement of the reference op sequence) on this host.
+A plain run sets up, warms up, times the K headline steps and prints the result line
+(``ms_per_step`` = milliseconds per timed step).  ``--dump-outputs DIR`` also writes what
+the last timed step computed (the post-rollout TensorDict columns and the reward) as
+``DIR/<name>.npy``; the inputs are seeded, so two builds run with the same arguments can
+be compared output for output.
+
+``--full`` adds everything else (``modes``): the same episode stepwise (one launch per
+env step, TensorDict state in HBM between steps, HIP graph), the in-kernel
+nearest-unvisited policy, SLAP (examples/slap.py instance, B = 16,384), the drop-in, POMO
+and CVRP paths, the copy probe beside the roofline, and ``cpu_baseline``: the CPU oracle
+(plain-PyTorch restatement of the reference op sequence) on this host.  Those legs time a
+fifth of ``--steps`` episodes each, ``--steps`` counted up to 100 (``--mode-steps K`` sets
+the number directly): a ``--full`` run stays within minutes whatever ``--steps`` is.
 """
 from __future__ import annotations
 
@@ -34,6 +43,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 FP32_VECTOR_PEAK_TFS = 157.3  # MI355X FP32 vector (MI355X_MICROARCH.md)
+FULL_STEPS_CAP = 100  # --full: --steps beyond this no longer lengthens the other legs
 
 
 def parse():
@@ -44,8 +54,18 @@ def parse():
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--num-loc", type=int, default=100)
     ap.add_argument("--slap-batch", type=int, default=16384)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-modes", action="store_true", help="headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the benchmark measures: the "
+                         "stepwise / SLAP / drop-in / POMO / CVRP modes, the copy probe beside the "
+                         "roofline, the step kernels against a copy and the CPU baselines")
+    ap.add_argument("--mode-steps", type=int, default=0, metavar="K",
+                    help="with --full: timed episodes per leg beside the headline (default: a "
+                         f"fifth of --steps, --steps counted up to {FULL_STEPS_CAP})")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed headline step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-modes", action="store_true",
+                    help="with --full: skip the mode tables and the other workloads' CPU baselines")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU plumbing check: gloo ranks, the CPU oracle episode as the step "
                          "(no GPU, no HIP library); rehearses --gpus N launches in a container")
@@ -141,6 +161,34 @@ def tsp_inputs(b, n, rank, salt=0):
     torch.manual_seed(4321 + rank + 104729 * salt)
     acts = torch.rand(b, n).argsort(1)
     return locs, acts
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor of `arrays` (all with the batch as their leading dimension)
+    as ``dirname/<name>.npy``; floating-point and bool columns as float32, integer columns as
+    float64 (exact for every index the envs produce).  Above 64 MB in all, the same sorted
+    sample of instances (``randperm`` from a generator seeded with 0) is kept from every
+    array and its instance indices are written as ``rows.npy``."""
+    import numpy as np
+
+    conv = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        conv[name] = t.to(torch.float32 if t.dtype.is_floating_point or t.dtype == torch.bool
+                          else torch.float64).contiguous()
+    total = sum(t.numel() * t.element_size() for t in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        b = next(iter(conv.values())).shape[0]
+        keep = max(1, DUMP_LIMIT_BYTES // (-(-total // b) + 8))
+        rows = torch.randperm(b, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        conv = {name: t[rows].contiguous() for name, t in conv.items()}
+        conv["rows"] = rows.to(torch.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in conv.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.numpy())
 
 
 MALL_BYTES = 256 << 20  # Infinity Cache (MI355X_MICROARCH.md, chip-level parameters)
@@ -499,7 +547,7 @@ def main():
     if args.dry_run:
         return dry_run(args, world, rank, dev)
     from rl4co_slap_amd import _native
-    from rl4co_slap_amd.rollout.engine import TSPFusedEpisode, TSPStepwiseEpisode
+    from rl4co_slap_amd.rollout.engine import TSPFusedEpisode
 
     _native.load()
     b, n = args.batch, args.num_loc
@@ -519,6 +567,11 @@ def main():
     s = lambda: next(cyc)(sh)  # noqa: E731
     wall, ev = timed(s, args.steps, args.warmup, world, dev)
     assert all(int(e.status.item()) == 0 for e in eps), "invalid tour in the benchmark episode"
+    if args.dump_outputs and rank == 0:
+        # the episode the last timed step launched: the TensorDict columns and the reward a
+        # caller of the fused episode receives ("actions" echoes the input and is left out)
+        fin = eps[(args.warmup + args.steps - 1) % n_rot].final_state()
+        dump_outputs(args.dump_outputs, {key: v for key, v in fin.items() if key != "actions"})
     del eps
     t = max_over_ranks(wall, world, dev)
     value = world * b * n * args.steps / t
@@ -553,15 +606,49 @@ def main():
                      "achieved_wall": bytes_per_launch / (t / args.steps) / 1e9,
                      "frac_wall": bytes_per_launch / (t / args.steps) / 1e9 / HBM_PEAK_GBS,
                      "traffic_source": traffic_src,
-                     "bytes_per_launch": bytes_per_launch, "launch_us": per_launch * 1e6,
-                     "copy_probe": copy_probe(bytes_per_launch, dev, args.steps)},
+                     "bytes_per_launch": bytes_per_launch, "launch_us": per_launch * 1e6},
     }
     out["config"]["input_batches_cycled"] = n_rot
+    if args.full:
+        out["roofline"]["copy_probe"] = copy_probe(bytes_per_launch, dev,
+                                                   min(args.steps, FULL_STEPS_CAP))
+        full_legs(args, out, world, rank, dev, locs, acts, locs_cpu, acts_cpu, sh)
+    if rank == 0:
+        out["build"] = _native.provenance()  # the sources the measured library came from
+        out["summary"] = summarize(out)
+        # contract keys first, the long mode tables of a --full run next, and the short
+        # records a reader of the end of the line needs LAST: the stepwise / SLAP-65,536
+        # figures and the summary of every mode end the line
+        order = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                 "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                 "roofline", "cpu_baseline"]
+        last = ["tsp_stepwise", "tsp_stepwise_chunked", "slap_b65536", "summary"]
+        final = {key: out[key] for key in order if key in out}
+        final.update({key: v for key, v in out.items() if key not in final and key not in last})
+        final.update({key: out[key] for key in last if key in out})
+        print(json.dumps(final), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
 
+
+def mode_steps(args):
+    """Timed episodes per --full leg: a fifth of --steps, at least 3.  A --steps sized for
+    the 19 us headline launch (tens of thousands) must not stretch the millisecond-long
+    stepwise and drop-in episodes to hours, so --steps counts up to FULL_STEPS_CAP only;
+    --mode-steps K sets the number directly."""
+    return args.mode_steps or max(3, min(args.steps, FULL_STEPS_CAP) // 5)
+
+
+def full_legs(args, out, world, rank, dev, locs, acts, locs_cpu, acts_cpu, sh):
+    """--full: every leg beside the headline, added to `out` -- the stepwise TSP and SLAP
+    episodes, the mode tables, the step kernels against a copy and the CPU baselines."""
+    from rl4co_slap_amd.rollout.engine import TSPFusedEpisode, TSPStepwiseEpisode
+
+    b, n = args.batch, args.num_loc
     # ---- the contract-faithful per-step TSP loop (SURVEY 8d): one launch per env step,
     # every step's TensorDict state written to and re-read from HBM (2N+50 B per env-step,
     # + the episode reward's 16N+4 B amortised), HIP graph of reset + N steps + reward
-    k = max(3, args.steps // 5)
+    k = out["config"]["mode_steps"] = mode_steps(args)
     sw = TSPStepwiseEpisode(locs, acts, policy="teacher", check=True).capture()
     wall_s, ev_s = timed(sw.replay, k, 2, world, dev)
     assert int(sw.status.item()) == 0, "TSP stepwise episode status"
@@ -681,22 +768,6 @@ def main():
             out["cpu_baseline_slap"] = cpu_baseline_slap()
             out["cpu_baseline_cvrp"] = cpu_baseline_cvrp()
             out["cpu_baseline_pomo"] = cpu_baseline_pomo()
-    if rank == 0:
-        out["build"] = _native.provenance()  # the sources the measured library came from
-        out["summary"] = summarize(out)
-        # contract keys first, the long mode tables next, and the short records a reader
-        # (and the driver's stdout tail) needs LAST: the stepwise / SLAP-65,536 figures and
-        # the summary of every mode end the line
-        order = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
-                 "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
-                 "roofline", "cpu_baseline"]
-        last = ["tsp_stepwise", "tsp_stepwise_chunked", "slap_b65536", "summary"]
-        final = {key: out[key] for key in order if key in out}
-        final.update({key: v for key, v in out.items() if key not in final and key not in last})
-        final.update({key: out[key] for key in last if key in out})
-        print(json.dumps(final), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 def pmc_sq_issue(target, kernel):
