@@ -118,10 +118,13 @@ def load():
         lib.co_build_info.restype = ctypes.c_char_p
         lib.co_build_info.argtypes = []
         if hasattr(lib, "co_variant_timing_cut") or hasattr(lib, "co_variant_timing_cut_decode"):
-            # a diagnostic build (csrc/co_diag.hpp: CO_DIAG_* / CO_CVRP_CUT / CO_CVRP_RCUT):
-            # its results and status bits are wrong by design.  In the product's slot it is
-            # refused; a measurement tool that points LIB_PATH at a variant (or sets
-            # CO_ALLOW_DIAG_LIB=1) gets a warning.
+            # a diagnostic build: its results and status bits are wrong by design.  Every
+            # such switch is a CO_DIAG_* of csrc/co_diag.hpp and exports
+            # co_variant_timing_cut_decode; co_variant_timing_cut was the marker of the
+            # retired CVRP timing cuts and is still refused, because a variant library
+            # built from older sources may lie around.  In the product's slot a marked
+            # library is refused; a measurement tool that points LIB_PATH at a variant (or
+            # sets CO_ALLOW_DIAG_LIB=1) gets a warning.
             msg = (f"rl4co_slap_amd: {LIB_PATH} is a diagnostic build (timing cut / counting "
                    "variant): its results and status bits are not valid")
             if LIB_PATH == _PRODUCT_LIB_PATH and not os.environ.get("CO_ALLOW_DIAG_LIB"):

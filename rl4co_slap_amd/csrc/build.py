@@ -21,7 +21,7 @@ SOURCES = ["tsp.hip", "cvrp.hip", "slap.hip", "ops.hip", "decode_step.hip", "dec
            "decode_env.hip",
            "rollout.hip",
            "nearest.hip"]
-HEADERS = ["co_common.hpp", "co_tile.hpp", "co_math.hpp", "decode_common.hpp"]
+HEADERS = ["co_common.hpp", "co_tile.hpp", "co_math.hpp", "co_diag.hpp", "decode_common.hpp"]
 ARCH = "gfx950"
 
 

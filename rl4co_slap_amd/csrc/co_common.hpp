@@ -19,47 +19,6 @@ __device__ __forceinline__ int wave_in_block() {
   return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 }
 
-// Streaming accesses (round 6): data a launch reads once or writes once goes through the
-// non-temporal path (`nt` loads / stores: gfx950 streams them past the caches' normal
-// retention).  Measured: a 2 GiB copy 6.2 -> 6.6 TB/s, the headline launch 23.0 -> 20.7
-// us.  NT = false gives the plain access (kernels pass their own switch).
-template <bool NT, typename T>
-__device__ __forceinline__ T ld_s(const T* p) {
-  if constexpr (NT && (sizeof(T) == 4 || sizeof(T) == 8) && !__is_class(T)) {
-    return __builtin_nontemporal_load(p);
-  } else if constexpr (NT && sizeof(T) == 8) {  // float2 and other 8-byte structs
-    const unsigned long long u = __builtin_nontemporal_load(reinterpret_cast<const unsigned long long*>(p));
-    T v;
-    __builtin_memcpy(&v, &u, 8);
-    return v;
-  } else if constexpr (NT && sizeof(T) == 16) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 u = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-    T v;
-    __builtin_memcpy(&v, &u, 16);
-    return v;
-  } else {
-    return *p;
-  }
-}
-template <bool NT, typename T>
-__device__ __forceinline__ void st_s(T* p, T v) {
-  if constexpr (NT && (sizeof(T) == 1 || sizeof(T) == 4 || sizeof(T) == 8) && !__is_class(T)) {
-    __builtin_nontemporal_store(v, p);
-  } else if constexpr (NT && sizeof(T) == 8) {
-    unsigned long long u;
-    __builtin_memcpy(&u, &v, 8);
-    __builtin_nontemporal_store(u, reinterpret_cast<unsigned long long*>(p));
-  } else if constexpr (NT && sizeof(T) == 16) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 u;
-    __builtin_memcpy(&u, &v, 16);
-    __builtin_nontemporal_store(u, reinterpret_cast<u32x4*>(p));
-  } else {
-    *p = v;
-  }
-}
-
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
@@ -278,6 +237,51 @@ __device__ __forceinline__ void grp_argmin_split(float& v, int& idx) {
   v = m;
 }
 
+// ---------------------------------------------------------------------------
+// The candidate order of the SLAP closest-free policy: u64 keys (distance key << 32 |
+// location), sorted ascending once per lane (slap_group_kernel, slap_closest_steps_kernel).
+//
+// Order-preserving u32 of a distance: -0.0 keyed as +0.0 (d + 0.0 is +0.0 for d = -0.0, d
+// otherwise), so the two tie as in argmin's float compare and the index decides; 4 VALU.
+// +inf keys as kDistKeyInf, and a key not below it is never chosen.  Open: a
+// NaN with its sign bit set (0xffc00000) keys below every finite distance and is chosen
+// first, where the single-step scan's `d < best` never picks a NaN; giving every NaN the
+// +inf key changes results, so it is not done yet -- and then here, for both kernels.
+constexpr uint32_t kDistKeyInf = 0xff800000u;
+__device__ __forceinline__ uint32_t dist_key(float d) {
+  const uint32_t u = __float_as_uint(d + 0.0f);
+  return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
+}
+__device__ __forceinline__ uint32_t key_sel32(uint64_t m, uint32_t t, uint32_t f) {
+  uint32_t r;
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m));
+  return r;
+}
+// compare-exchange with one v_cmp_lt_u64 and four selects on its lane mask (written as
+// two ternaries the compiler emits a second, `gt`, compare for the max)
+__device__ __forceinline__ void key_cswap(uint64_t& a, uint64_t& b) {
+  const uint64_t lt = __builtin_amdgcn_ballot_w64(a < b);
+  const uint32_t alo = (uint32_t)a, ahi = (uint32_t)(a >> 32), blo = (uint32_t)b,
+                 bhi = (uint32_t)(b >> 32);
+  a = ((uint64_t)key_sel32(lt, ahi, bhi) << 32) | key_sel32(lt, alo, blo);
+  b = ((uint64_t)key_sel32(lt, bhi, ahi) << 32) | key_sel32(lt, blo, alo);
+}
+// ascending sort of E u64 keys in registers (Batcher odd-even merge network)
+template <int E>
+__device__ __forceinline__ void sort_keys(uint64_t (&k)[E]) {
+  static_assert((E & (E - 1)) == 0, "E must be a power of two");
+#pragma unroll
+  for (int p = 1; p < E; p <<= 1)
+#pragma unroll
+    for (int q = p; q > 0; q >>= 1)
+#pragma unroll
+      for (int j = q % p; j + q < E; j += 2 * q)
+#pragma unroll
+        for (int i = 0; i < q; ++i)
+          if (i + j + q < E && (i + j) / (2 * p) == (i + j + q) / (2 * p))
+            key_cswap(k[i + j], k[i + j + q]);
+}
+
 typedef __attribute__((address_space(3))) void lds_void;
 
 // Copy `nbytes` contiguous bytes global -> LDS with LDS-DMA (global_load_lds_dwordx4):
@@ -285,10 +289,7 @@ typedef __attribute__((address_space(3))) void lds_void;
 // round trip, all pieces in flight before the single wait.  `src` and `dst` must be
 // 16-byte aligned; a tail of < 16 bytes is copied with plain loads.  Ends with the
 // vmcnt drain + workgroup barrier that make the tile visible.
-#ifndef CO_STAGE_AUX
-#define CO_STAGE_AUX 0  // cache-policy bits of stage_bytes_lds's LDS-DMA (2 = nt)
-#endif
-template <int AUX = CO_STAGE_AUX>
+template <int AUX = 0>  // the loads' cache-policy bits (sc0 / nt / sc1)
 __device__ __forceinline__ void stage_bytes_lds(const unsigned char* __restrict__ src, int nbytes,
                                                 unsigned char* dst) {
   const int lane = threadIdx.x & 63, wave = wave_in_block(), nw = blockDim.x >> 6;

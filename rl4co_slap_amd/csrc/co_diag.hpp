@@ -1,4 +1,6 @@
 // Diagnostic builds: the -DCO_DIAG_* switches of the measurement tools, in one place.
+// These are the only switches that make the library compute something else than the
+// product does; a new one belongs here, so that it raises the marker below.
 //
 // The product library (csrc/build.py) defines none of them; every hook below is then a
 // compile-time false and the compiler drops the code it guards.  Tools build variants of
@@ -6,6 +8,8 @@
 // time or count one part of a kernel; such a library exports co_variant_timing_cut_decode
 // (decode_step.hip, for any of the switches below), and _native.load() refuses it in the
 // product's slot (_lib/libco_env.so) and only warns when a tool points LIB_PATH at it.
+// This header is one of build.py's HEADERS: editing it rebuilds the library and changes
+// its source hash.
 #pragma once
 
 namespace co {

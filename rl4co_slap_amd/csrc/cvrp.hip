@@ -12,13 +12,6 @@
 
 using namespace co;
 
-#if CO_CVRP_CUT || CO_CVRP_RCUT
-// timing-diagnostic builds (tools/build_variants.sh) cut work out of the step / reward
-// kernels: their results and status bits are wrong by design.  The marker makes
-// _native.load() warn loudly for any library built this way.
-extern "C" __attribute__((visibility("default"))) const int co_variant_timing_cut = 1;
-#endif
-
 namespace {
 
 // Writes visited_out (optional update at column `a`), the action mask and returns
@@ -123,9 +116,6 @@ __global__ __launch_bounds__(256) void cvrp_step_kernel(
 // depot byte of each row is patched into its chunk after the barrier, so every byte of
 // the mask tile is written once by a 16-B store.  `not_done` (optional) receives one
 // atomicAdd per workgroup: the number of its rows that are not done.
-#ifndef CO_CVRP_QUAD
-#define CO_CVRP_QUAD 1  // co_cvrp_step takes the row-group kernel (below) when it can
-#endif
 #ifndef CO_CVRP_Q
 #define CO_CVRP_Q 1  // row groups per wave in the row-group kernel
 #endif
@@ -177,13 +167,8 @@ __global__ __launch_bounds__(THREADS) void cvrp_step_tile_kernel(
     if (c < nchunks) v[k] = tile_load(vsrc, c << 4, nbytes, true);
   }
   // demand tile -> LDS by LDS-DMA; the helper's vmcnt(0) + barrier also covers the loads above
-#if CO_CVRP_CUT & 1  // timing diagnostic only (tools/diag_cvrp_step.py): no demand tile
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-#else
   stage_bytes_lds(reinterpret_cast<const unsigned char*>(demand + row0 * N), rows * N * 4,
                   reinterpret_cast<unsigned char*>(s_dem));
-#endif
   if (tid < rows) {  // cvrp/env.py:79-85
     const bool bad = a_raw < 0 || a_raw > N;
     if (bad) set_status(status, CO_ST_INDEX_RANGE);
@@ -214,13 +199,6 @@ __global__ __launch_bounds__(THREADS) void cvrp_step_tile_kernel(
     const float u1 = has1 ? s_u[r1] : 0.f, cp1 = has1 ? s_cap[r1] : 0.f;
     const int dbase = off - r0 - 1;  // s_dem index of byte j: dbase + j (row r0), one less (r1)
     uint32_t w[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-#if CO_CVRP_CUT & 2  // timing diagnostic only: no per-byte update
-    s_part[2 * ch] = 0;
-    s_part[2 * ch + 1] = 0;
-    tile_store(vdst, off, nbytes, true, v[k]);
-    m[k] = v[k];
-    continue;
-#endif
     // all 16 demand reads issued before any use (a short-circuit `||` would put each
     // behind a branch and an lgkmcnt(0) wait)
     // 17 consecutive floats from one base (static offsets, no per-read address math): byte
@@ -889,7 +867,6 @@ __global__ __launch_bounds__(WAVES * 64) void cvrp_reward_kernel(
         for (int k = lane; k < nseg; k += 64) cur_v[k] = nxt_v[k] = 0.f;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
-#if !CO_CVRP_RCUT
         // an overflow is final (stop); a NaN demand overflows; at most nseg passes
         for (int pass = 0, again = 1; again && pass < nseg; ++pass) {
           bool changed = false;
@@ -922,7 +899,6 @@ __global__ __launch_bounds__(WAVES * 64) void cvrp_reward_kernel(
           cur_v = nxt_v;
           nxt_v = tmp;
         }
-#endif
         over = __any(over);
         if (over && lane == 0) set_status(status, CO_ST_OVER_CAPACITY);
       }
@@ -995,11 +971,6 @@ __global__ __launch_bounds__(64 * Q) void cvrp_reward_tile_kernel(
   const bool live = lane < rows;
   const int64_t b = live ? row0 + lane : row0;  // dead lanes mirror lane 0's loads
   const int64_t* ap = acts + b * sb;             // this lane's column (row t at ap[t * st])
-#ifdef CO_CVRPR_TIMING  // diagnostic: phase clocks of each workgroup into reward[row0 + i]
-  __shared__ unsigned long long s_tm[8];
-  const unsigned long long tm0 = __builtin_readcyclecounter();
-  if (threadIdx.x < 8) s_tm[threadIdx.x] = 0;
-#endif
   // roles; each issues its first action rows before the tiles are staged (the staging
   // helper's vmcnt(0) + barrier then covers them too)
   const bool scanner = check && q == 0;
@@ -1036,15 +1007,12 @@ __global__ __launch_bounds__(64 * Q) void cvrp_reward_tile_kernel(
     for (int base = (q - 1) * 1024; q > 0 && base < d16; base += (Q - 1) * 1024)
       if (base + lane * 16 < d16)
         __builtin_amdgcn_global_load_lds((const void*)(dsrc + base + lane * 16),
-                                         (lds_void*)(smem + L.dem + base), 16, 0, CO_STAGE_AUX);
+                                         (lds_void*)(smem + L.dem + base), 16, 0, 0);
     for (int k = d16 + (int)threadIdx.x; k < dbytes; k += 64 * Q) smem[L.dem + k] = dsrc[k];
   }
   stage_bytes_lds(reinterpret_cast<const unsigned char*>(locs + row0 * NC), rows * NC * 8,
                   smem + L.xy);  // ends with vmcnt(0) + a barrier
   const float2* xy = s_xy + (size_t)lane * NC;
-#ifdef CO_CVRPR_TIMING
-  if (threadIdx.x == 0) s_tm[1] = __builtin_readcyclecounter() - tm0;
-#endif
   double len = 0.0;
   if (scanner) {
     // ---- scanner (cvrp/env.py:177-190 in step order).  Only the low dword of each
@@ -1092,9 +1060,6 @@ __global__ __launch_bounds__(64 * Q) void cvrp_reward_tile_kernel(
     if (k < nb) scan(a0, k * SU);
     if (k + 1 < nb) scan(a1, (k + 1) * SU);
     s_over[lane] = over;
-#ifdef CO_CVRPR_TIMING
-    if (lane == 0) s_tm[2] = __builtin_readcyclecounter() - tm0;
-#endif
   } else {
     // ---- walkers: edges (+ visited words) over round-robin U-step batches
     bool range = false;
@@ -1142,9 +1107,6 @@ __global__ __launch_bounds__(64 * Q) void cvrp_reward_tile_kernel(
     if (j < nbt) run(bufA, prevA, j);
     if (range) s_range[lane] = 1;
     if (check && nonzero) atomicAdd(&s_cnt[lane], nonzero);
-#ifdef CO_CVRPR_TIMING
-    if (lane == 0) atomicMax(&s_tm[3], __builtin_readcyclecounter() - tm0);
-#endif
   }
   const float2 dep = xy[0];
   __syncthreads();  // episode walked: the demand rows are free for the partial sums
@@ -1170,10 +1132,6 @@ __global__ __launch_bounds__(64 * Q) void cvrp_reward_tile_kernel(
       if (__any(invalid) && lane == 0) set_status(status, CO_ST_INVALID_TOUR);
       if (__any(ovr) && lane == 0) set_status(status, CO_ST_OVER_CAPACITY);
     }
-#ifdef CO_CVRPR_TIMING
-    if (lane == 0) s_tm[4] = __builtin_readcyclecounter() - tm0;
-    if (lane < 5 && lane < rows) reward[row0 + lane] = (float)s_tm[lane];
-#endif
   }
 }
 
@@ -1222,7 +1180,7 @@ extern "C" int co_cvrp_step(int64_t B, int64_t N, const int64_t* action, const f
   constexpr int G = CO_CVRP_G, Q = CO_CVRP_Q;
   // dwords per lane: ceil(ceil((N+4)/4) / G), at most 4
   const int kpl = (int)((NC + 6) / 4 + G - 1) / G;
-  if (CO_CVRP_QUAD && rows_ok && kpl <= 4) {
+  if (rows_ok && kpl <= 4) {
     // 16 waves per workgroup when the not-done counter is wanted (fewer atomics), else 4
     const int waves = not_done ? 16 : 4;
     const int64_t rows_per_wg = (int64_t)(64 / G) * Q * waves;

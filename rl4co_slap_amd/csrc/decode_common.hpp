@@ -10,8 +10,6 @@
 #pragma once
 // Shared by decode_step.hip (co_decode_step[_ex], beam search) and decode_tsp.hip
 // (co_tsp_decode_step): two translation units, compiled in parallel.
-#include <type_traits>
-
 #include "co_common.hpp"
 #include "co_diag.hpp"
 #include "co_math.hpp"
@@ -60,12 +58,6 @@ constexpr int kOptClip = 1, kOptTemp = 2, kOptFast = 4, kOptCert = 8;
 // -inf already (no per-slot row-bound select in the exp sum), the log on v_log_f32, the
 // group max on ordered ints, the lane's top two kept for the certification
 constexpr int kOptLean = 16;
-#ifndef CO_TANH_COMPACT
-#define CO_TANH_COMPACT 1  // GreedyRow: exact tanh of allowed elements only, wave-compacted
-#endif
-#ifndef CO_TANH_CHAINS
-#define CO_TANH_CHAINS 2  // packed tanh evaluations per lane and loop iteration (1 or 2)
-#endif
 
 template <int OPT>
 __device__ __forceinline__ float clip_tanh(float x) {
@@ -133,7 +125,6 @@ __device__ __forceinline__ void wave_tanh_compact(float (&v)[EPL], const bool (&
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if CO_TANH_CHAINS == 2
   for (int j = lane; j < total; j += 128) {  // two independent f64 chains per lane
     const bool two = j + 64 < total;
     const float x0 = wave_lds[j], x1 = two ? wave_lds[j + 64] : 0.f;
@@ -141,9 +132,6 @@ __device__ __forceinline__ void wave_tanh_compact(float (&v)[EPL], const bool (&
     wave_lds[j] = y0;
     if (two) wave_lds[j + 64] = y1;
   }
-#else
-  for (int j = lane; j < total; j += 64) wave_lds[j] = tanh_cr(wave_lds[j]);
-#endif
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -441,21 +429,6 @@ __device__ __forceinline__ float lane_select(bool c, float t, float f) {
   return r;
 }
 
-#ifndef CO_DECODE_NT
-#define CO_DECODE_NT 0  // logits chunks by non-temporal loads (r06: POMO 1.80 -> 1.83 ms, CVRP
-                        // decode step 10.1 -> 10.6 us: kept off)
-#endif
-template <class F>
-__device__ __forceinline__ F ld_logit4(const F* p) {
-  if constexpr (CO_DECODE_NT && std::is_same<F, float4>::value) {
-    return ld_s<true>(p);
-  } else if constexpr (CO_DECODE_NT) {
-    return __builtin_nontemporal_load(p);
-  } else {
-    return *p;
-  }
-}
-
 template <int RL, int EPL, int VW>
 struct GreedyRow {
   static_assert(EPL % 4 == 0, "GreedyRow keeps the mask in u32 words");
@@ -477,7 +450,7 @@ struct GreedyRow {
       uint32_t m = 0u;
       float xf[4] = {0.f, 0.f, 0.f, 0.f};
       if (valid && c + 4 <= N) {
-        const F x = ld_logit4(reinterpret_cast<const F*>(lrow + c));
+        const F x = *reinterpret_cast<const F*>(lrow + c);
         xf[0] = x[0];
         xf[1] = x[1];
         xf[2] = x[2];
@@ -514,7 +487,7 @@ struct GreedyRow {
     for (int j = 0; j < EPL / 4; ++j) {  // every load issued before the first use
       const int c = c0 + 4 * j;
       const int cb = c < N - 4 ? c : N - 4;
-      x[j] = ld_logit4(reinterpret_cast<const F*>(lrow + cb));
+      x[j] = *reinterpret_cast<const F*>(lrow + cb);
       w[j] = mrow ? (uint32_t) * reinterpret_cast<const M*>(mrow + cb) : 0x01010101u;
     }
 #pragma unroll
@@ -609,7 +582,7 @@ struct GreedyRow {
                                                  float* lds_row) {
     const float NEG_INF = -__builtin_inff();
     // exact tanh clipping: tanh of the allowed elements, wave-compacted (above)
-    constexpr bool kCompact = COMPACT && (OPT & kOptClip) && !(OPT & kOptFast) && CO_TANH_COMPACT;
+    constexpr bool kCompact = COMPACT && (OPT & kOptClip) && !(OPT & kOptFast);
     if constexpr (kCompact) tanh_allowed_compact(lds_row - (lane_id() / RL) * (RL * EPL));
     float m = NEG_INF, m2 = NEG_INF;
     constexpr bool kPairs = (OPT & kOptLean) != 0 && (OPT & kOptClip) != 0 && (OPT & kOptTemp) == 0;
@@ -967,14 +940,7 @@ __global__ __launch_bounds__(256) void tsp_decode_step_kernel(
 // Greedy decode step fused with TSPEnv._step on the GreedyRow engine (the POMO /
 // multistart-greedy hot loop); same outputs as tsp_decode_step_kernel in greedy mode.
 // The mask words are updated in registers (the selected byte cleared) and stored back.
-// STAGE (round 6): the wave's RPW logits rows and mask rows (contiguous: lstride == N,
-// N % 4 == 0, 16-byte aligned) arrive by non-temporal LDS-DMA -- whole-line streams --
-// and the lanes read their chunks from LDS; the certified fallback re-reads the row from
-// memory as before.
-__host__ __device__ inline size_t tsp_dstage_bytes(int rpw, int N) {
-  return (size_t)rpw * N * 4 + (((size_t)rpw * N + 15) & ~(size_t)15);
-}
-template <int RL, int EPL, int VW, int OPT, bool STAGE = false>
+template <int RL, int EPL, int VW, int OPT>
 __global__ __launch_bounds__(256) void tsp_decode_greedy_kernel(
     int64_t B, int N, const float* __restrict__ logits, int64_t lstride,
     const uint8_t* __restrict__ mask_in, float clip, float temp, int64_t* __restrict__ action_out,
@@ -984,7 +950,6 @@ __global__ __launch_bounds__(256) void tsp_decode_greedy_kernel(
     uint8_t* __restrict__ step_reward, float* __restrict__ ll_accum, int32_t* status) {
   constexpr int RPW = 64 / RL;
   __shared__ __attribute__((aligned(16))) float lds[4 * 64 * EPL];
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_dstage[];
   const int lane = lane_id(), sl = lane % RL, grp = lane / RL, c0 = sl * EPL;
   const int64_t wid = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
   const unsigned long long gmask = RL == 64 ? ~0ull : (((1ull << RL) - 1ull) << (grp * RL));
@@ -1006,17 +971,7 @@ __global__ __launch_bounds__(256) void tsp_decode_greedy_kernel(
     GreedyRow<RL, EPL, VW> g;
     const float* lrow = logits + r * lstride;
     const uint8_t* mrow = mask_in + r * (int64_t)N;
-    if constexpr (STAGE) {
-      const int nr = (int)(B - base < RPW ? B - base : RPW);
-      unsigned char* sw = s_dstage + (size_t)wave_in_block() * tsp_dstage_bytes(RPW, N);
-      wave_dma<2>(reinterpret_cast<const unsigned char*>(logits + base * N), nr * N * 4, sw);
-      wave_dma<2>(mask_in + base * N, nr * N, sw + (size_t)RPW * N * 4);
-      wave_dma_wait();
-      g.load(valid, N, reinterpret_cast<const float*>(sw) + grp * N, sw + (size_t)RPW * N * 4 + grp * N,
-             c0);
-    } else {
-      g.load(valid, N, lrow, mrow, c0);
-    }
+    g.load(valid, N, lrow, mrow, c0);
     float lp, L;
     const int sel = greedy_row<OPT>(g, valid, N, clip, temp, sl, c0,
                                            group_scratch<RL, EPL>(lds, grp), L, lp, lrow, mrow);

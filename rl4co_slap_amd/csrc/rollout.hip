@@ -75,10 +75,6 @@ __device__ __forceinline__ void zero_tile_out(int nbytes, uint8_t* __restrict__ 
   for (int k = n16 + tid; k < nbytes; k += blockDim.x) dst[k] = 0;
 }
 
-#ifndef CO_TEACH_ZFAST
-#define CO_TEACH_ZFAST 1  // all-visited tiles store zero mask rows without the LDS expansion
-#endif
-
 // LDS bytes of the TSP teacher kernel's coordinate tile region: [64][N] float2, or the
 // post-episode scratch (mask bytes, Q x 64 partial sums, last node) if larger.
 __host__ __device__ inline size_t tsp_tile_bytes(int N, int Q) {
@@ -104,12 +100,8 @@ __host__ __device__ inline size_t tsp_tile_bytes(int N, int Q) {
 #ifndef CO_TEACH_U
 #define CO_TEACH_U 8
 #endif
-// NB > 0: a wave's whole step range (<= NB*U steps) is loaded into registers at the
-// kernel's start, in flight together with the coordinate staging, so the walk itself
-// waits on LDS only; NB == 0: U-step batches double-buffered during the walk (long N).
-#ifndef CO_TEACH_NB
-#define CO_TEACH_NB 0
-#endif
+// NB: always 0 (the U-step batches are double-buffered during the walk); the parameter
+// only keeps the kernels' names.
 template <int NW, int Q, bool STATE, int NB = 0>
 __global__ __launch_bounds__(64 * Q) void tsp_teacher_kernel(
     int64_t B, int N, const float2* __restrict__ locs, int64_t LB,
@@ -147,18 +139,7 @@ __global__ __launch_bounds__(64 * Q) void tsp_teacher_kernel(
   const int nfull = (t_hi - t_lo) / U;
   // wave 0: step 0's action; wave q > 0: the action before its range (previous node)
   const int64_t a_prev = ap[(int64_t)(q == 0 ? 0 : t_lo - 1) * B];
-  int64_t pre[NB > 0 ? NB * U : 1];
-  if constexpr (NB > 0) {
-    // every step of the range at once (rows past t_hi re-read the range's last row,
-    // in bounds, never used); the walk below then waits on LDS only
-#pragma unroll
-    for (int j = 0; j < NB * U; ++j) {
-      const int tj = t_lo + j < t_hi ? t_lo + j : (t_hi > 0 ? t_hi - 1 : 0);
-      pre[j] = ap[(int64_t)tj * B];
-    }
-  } else if (nfull > 0) {
-    load(bufA, t_lo);
-  }
+  if (nfull > 0) load(bufA, t_lo);
   if (q == 0) {
     for (int k = 0; k < NW; ++k) {
       const int lo = k * 64;
@@ -236,33 +217,20 @@ __global__ __launch_bounds__(64 * Q) void tsp_teacher_kernel(
           a = av[u];
         }
     };
-    if constexpr (NB > 0) {
-      const int cnt = t_hi - t_lo;
+    int k = 0;
+    for (; k + 1 < nfull; k += 2) {
+      load(bufB, t_lo + (k + 1) * U);
+      run(bufA, U);
+      load(bufA, t_lo + (k + 2) * U);
+      run(bufB, U);
+    }
+    if (k < nfull) run(bufA, U);
+    const int tail = t_hi - t_lo - nfull * U;  // < U steps left
+    if (tail > 0) {
+      const int t0 = t_lo + nfull * U;
 #pragma unroll
-      for (int kb = 0; kb < NB; ++kb) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) bufA[u] = pre[kb * U + u];
-        if (cnt >= (kb + 1) * U)
-          run(bufA, U);  // full batch: straight-line code (a compile-time count)
-        else if (cnt > kb * U)
-          run(bufA, cnt - kb * U);
-      }
-    } else {
-      int k = 0;
-      for (; k + 1 < nfull; k += 2) {
-        load(bufB, t_lo + (k + 1) * U);
-        run(bufA, U);
-        load(bufA, t_lo + (k + 2) * U);
-        run(bufB, U);
-      }
-      if (k < nfull) run(bufA, U);
-      const int tail = t_hi - t_lo - nfull * U;  // < U steps left
-      if (tail > 0) {
-        const int t0 = t_lo + nfull * U;
-#pragma unroll
-        for (int u = 0; u < U; ++u) bufB[u] = (u < tail) ? ap[(int64_t)(t0 + u) * B] : 0;
-        run(bufB, tail);
-      }
+      for (int u = 0; u < U; ++u) bufB[u] = (u < tail) ? ap[(int64_t)(t0 + u) * B] : 0;
+      run(bufB, tail);
     }
   }
   // out-of-range actions seen by this wave (revisits: from the final words below)
@@ -294,7 +262,7 @@ __global__ __launch_bounds__(64 * Q) void tsp_teacher_kernel(
   // and are stored as zeros, without the LDS expansion and its read-back.
   int* s_flag = s_lasta + 64;  // [Q]
   bool all_empty = false;
-  if (STATE && CO_TEACH_ZFAST) {
+  if (STATE) {
     const bool wave_empty = __ballot(live && !empty) == 0ull;
     if (lane == 0) s_flag[q] = wave_empty;
     __syncthreads();
@@ -340,11 +308,11 @@ __global__ __launch_bounds__(64 * Q) void tsp_teacher_kernel(
 // Teacher-forced TSP episode on ROW-MAJOR actions [B, N] (element (b, t) at
 // acts[b*sb + t]: the reference's own [B, T] layout, ConstructivePolicy's `actions`):
 // G lanes per instance, lane sl owns the EPL consecutive steps t = sl*EPL + k.  Every
-// input is read as a contiguous row: MODE 2 (the headline's) stages a wave's GPW action
-// rows and GPW coordinate rows by LDS-DMA as two contiguous blocks and reads steps and
-// coordinate gathers from LDS; MODE 0 / 1 read the instance's 8N bytes of actions from
-// memory (scalar / 16-byte vectors) and gather its coordinates within one row (whole
-// lines, L2).  One block of instances per wave, all of B in flight.  The visited set
+// input is read as a contiguous row: MODE 3 (the headline's) stages a wave's GPW
+// coordinate rows by LDS-DMA as one contiguous block, loads the actions straight into
+// registers and gathers the coordinates from LDS; MODE 0 / 1 read the instance's 8N bytes
+// of actions from memory (scalar / 16-byte vectors) and gather its coordinates within one
+// row (whole lines, L2).  One block of instances per wave, all of B in flight.  The visited set
 // is a per-group LDS bitmap (no-return ds_or per step); the actions are a permutation iff
 // all N bits are set after the N steps (and every action is in range).  Edge lengths in
 // f32 (hardware sqrt, <= 1 ulp; reward parity is 1e-5 relative): within a lane, to the
@@ -354,42 +322,23 @@ __global__ __launch_bounds__(64 * Q) void tsp_teacher_kernel(
 #ifndef CO_ROWS_EPL112
 #define CO_ROWS_EPL112 7  // steps per lane for 96 < N <= 112 (16 lanes)
 #endif
-#ifndef CO_ROWS_DMA
-#define CO_ROWS_DMA 1  // the row kernel stages a wave's rows by LDS-DMA when it can
-#endif
 
-// LDS bytes per wave of the LDS-DMA variant: the wave's GPW coordinate rows and action
-// rows, contiguous in memory, land in LDS as two blocks of GPW*N*8 bytes.
+// LDS bytes per wave of MODE 3: the wave's GPW coordinate rows, contiguous in memory, land
+// in LDS as one block of GPW*N*8 bytes.
 __host__ __device__ inline size_t tsp_rows_wave_bytes(int gpw, int N) {
-  return (((size_t)gpw * N * 8 + 15) & ~(size_t)15) * 2;
+  return ((size_t)gpw * N * 8 + 15) & ~(size_t)15;
 }
 
-// MODE 0: scalar 8-byte action loads; 1: 16-byte vectors (16-byte aligned rows); 2: the
-// wave's GPW action and coordinate rows (contiguous: sb == N, consecutive coordinate
-// rows) staged by LDS-DMA as two contiguous blocks, steps and gathers then read from LDS.
+// MODE 0: scalar 8-byte action loads; 1: 16-byte vectors (16-byte aligned rows); 3: the
+// wave's GPW coordinate rows (consecutive rows, the actions contiguous: sb == N) staged by
+// LDS-DMA as one block, the actions loaded straight into registers, in flight with it.
 #ifndef CO_ROWS_WPB
 #define CO_ROWS_WPB 4  // waves per workgroup of the row kernel (r06: 2 / 8 / 16 slower)
 #endif
 // Round 6: the inputs are read once and the outputs written once, so the row kernel's
-// LDS-DMA loads carry the non-temporal hint (nt: streamed past the caches' normal
-// retention) and its mask rows are non-temporal stores -- 23.0 -> 20.7 us per launch at
-// B = 65,536 (HIP events, same box A/B; sc0 / sc1 variants measured no better).
-#ifndef CO_ROWS_AUX
-#define CO_ROWS_AUX 2  // cache-policy bits of the row kernel's LDS-DMA loads (2 = nt)
-#endif
-#ifndef CO_ROWS_NTST
-#define CO_ROWS_NTST 1  // non-temporal mask-row stores
-#endif
-#ifndef CO_ROWS_MODE3
-#define CO_ROWS_MODE3 1  // coordinates by LDS-DMA, actions loaded straight into registers
-                         // (r06: half the LDS per wave; 20.7 -> 19.1 us, same-box A/B)
-#endif
-#ifndef CO_ROWS_AV4
-#define CO_ROWS_AV4 0  // MODE 3: the actions as 16-byte pieces (odd EPL; r06: no faster, off)
-#endif
-#ifndef CO_ROWS_ANT
-#define CO_ROWS_ANT 0  // MODE 3: the action loads non-temporal (r06: 19.1 -> 35.7 us, partial lines)
-#endif
+// LDS-DMA loads carry the non-temporal hint (wave_dma<2>, nt: streamed past the caches'
+// normal retention) and its mask rows are non-temporal stores -- 23.0 -> 20.7 us per
+// launch at B = 65,536 (HIP events, same box A/B; sc0 / sc1 variants measured no better).
 template <int G, int EPL, int MODE, bool STATE>
 __global__ __launch_bounds__(64 * CO_ROWS_WPB) void tsp_teacher_rows_kernel(
     int64_t B, int N, const float2* __restrict__ locs, int64_t LB,
@@ -401,17 +350,14 @@ __global__ __launch_bounds__(64 * CO_ROWS_WPB) void tsp_teacher_rows_kernel(
   // 16-byte action pairs only when every lane's first step t0 = sl*EPL is even (the row
   // base is 16-byte aligned): an odd EPL takes the scalar loads
   // MODE 3: the coordinate rows by LDS-DMA (nt), the actions straight into registers
-  constexpr bool VEC = MODE == 1 && EPL % 2 == 0, DMA = MODE == 2 || MODE == 3,
-                 ADMA = MODE == 2;
+  constexpr bool VEC = MODE == 1 && EPL % 2 == 0, DMA = MODE == 3;
   __shared__ uint32_t s_bits[CO_ROWS_WPB][GPW][(G * EPL + 31) / 32];
   extern __shared__ __attribute__((aligned(16))) unsigned char s_rows[];  // DMA: per wave
   constexpr int NWB = (G * EPL + 31) / 32;
   const int lane = lane_id(), sl = lane % G, grp = lane / G, w = wave_in_block();
   uint32_t* bits = s_bits[w][grp];
-  const size_t half = DMA ? tsp_rows_wave_bytes(GPW, N) / 2 : 0;
-  unsigned char* s_w = s_rows + (DMA ? (size_t)w * (ADMA ? 2 : 1) * half : 0);
+  unsigned char* s_w = s_rows + (DMA ? (size_t)w * tsp_rows_wave_bytes(GPW, N) : 0);
   const float2* s_xy = reinterpret_cast<const float2*>(s_w);
-  const int64_t* s_act = reinterpret_cast<const int64_t*>(s_w + half);
   const int64_t wid = (int64_t)blockIdx.x * (blockDim.x >> 6) + w;
   const int nwords = (N + 31) >> 5;
   const int t0 = sl * EPL;
@@ -428,46 +374,16 @@ __global__ __launch_bounds__(64 * CO_ROWS_WPB) void tsp_teacher_rows_kernel(
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
       const int rows = (int)(B - base < GPW ? B - base : GPW);
       const int64_t lb = LB == B ? base : base % LB;
-      wave_dma<CO_ROWS_AUX>(reinterpret_cast<const unsigned char*>(locs + lb * N), rows * N * 8,
-                            s_w);
-      if constexpr (ADMA)
-        wave_dma<CO_ROWS_AUX>(reinterpret_cast<const unsigned char*>(acts + base * (int64_t)N),
-                              rows * N * 8, s_w + half);
+      wave_dma<2>(reinterpret_cast<const unsigned char*>(locs + lb * N), rows * N * 8, s_w);
     }
     int64_t av[EPL];
-    if constexpr (MODE == 3) {  // in flight with the DMA
-      if constexpr (CO_ROWS_AV4 && EPL % 2 == 1) {
-        // 16-byte pieces (8-byte aligned: gfx950 loads them whole), branch-free and inside
-        // the row: pair j starts at p = min(t0 + 2j, N - 2); when clamped, step t0 + 2j is
-        // N - 1 (its .y) or past N (masked below like every slot past N)
-        typedef long long i64x2a8 __attribute__((ext_vector_type(2), aligned(8)));
+    if constexpr (MODE == 3) {  // in flight with the DMA; slots past N re-read step N-1
 #pragma unroll
-        for (int k = 0; k + 1 < EPL; k += 2) {
-          const int p = t0 + k < N - 2 ? t0 + k : N - 2;
-          const i64x2a8 v = *reinterpret_cast<const i64x2a8*>(arow + p);
-          av[k] = p == t0 + k ? v.x : v.y;
-          av[k + 1] = v.y;
-        }
-        av[EPL - 1] = arow[t0 + EPL - 1 < N ? t0 + EPL - 1 : N - 1];
-      } else {  // slots past N re-read step N-1
-#pragma unroll
-        for (int k = 0; k < EPL; ++k)
-          av[k] = ld_s<CO_ROWS_ANT>(arow + (t0 + k < N ? t0 + k : N - 1));
-      }
+      for (int k = 0; k < EPL; ++k) av[k] = arow[t0 + k < N ? t0 + k : N - 1];
     }
-    if constexpr (DMA) {
-      __builtin_amdgcn_s_waitcnt(0);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+    if constexpr (DMA) wave_dma_wait();
     // the lane's EPL actions: 16-byte vectors when the row is 16-byte aligned
-    if constexpr (ADMA) {
-      // branch-free: slots past N re-read step N-1 (in the staged block); their
-      // contributions are masked below
-#pragma unroll
-      for (int k = 0; k < EPL; ++k) av[k] = s_act[grp * N + (t0 + k < N ? t0 + k : N - 1)];
-    } else if constexpr (MODE == 3) {
+    if constexpr (MODE == 3) {  // loaded above; the slots past N are masked below
     } else if constexpr (VEC) {
 #pragma unroll
       for (int k = 0; k < EPL; k += 2) {
@@ -566,10 +482,7 @@ __global__ __launch_bounds__(64 * CO_ROWS_WPB) void tsp_teacher_rows_kernel(
             const uint32_t nib = ~(bits[c4 >> 3] >> (4 * (c4 & 7))) & 0xfu;
             v = (nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21);
           }
-          if (CO_ROWS_NTST)
-            __builtin_nontemporal_store(v, reinterpret_cast<uint32_t*>(mrow + 4 * c4));
-          else
-            *reinterpret_cast<uint32_t*>(mrow + 4 * c4) = v;
+          __builtin_nontemporal_store(v, reinterpret_cast<uint32_t*>(mrow + 4 * c4));
         }
       } else {
         for (int c = sl; c < N; c += G)
@@ -595,55 +508,6 @@ __global__ __launch_bounds__(64 * CO_ROWS_WPB) void tsp_teacher_rows_kernel(
       if (sl == 0) reward_out[r] = -(float)len;
     }
   }
-}
-
-#ifndef CO_SLAP_CSWAP
-#define CO_SLAP_CSWAP 1  // one-compare comparator (asm selects) in the key sort (r06: -0.5 us)
-#endif
-#ifndef CO_SLAP_KEY2
-#define CO_SLAP_KEY2 1  // distance keys by an add of +0.0 and a sign mask (4 VALU instead of 6;
-                        // r06: -0.7 us at B = 65,536)
-#endif
-#ifndef CO_SLAP_OWNW
-#define CO_SLAP_OWNW 0  // the popping lane writes the assignment; free bits cleared after the
-                        // loop (r06: 43.4 -> 45.3 us at B = 65,536: off)
-#endif
-__device__ __forceinline__ uint32_t sel_u32(uint64_t m, uint32_t t, uint32_t f) {
-  uint32_t r;
-  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m));
-  return r;
-}
-// compare-exchange with one v_cmp_lt_u64 and four selects on its lane mask (written as
-// two ternaries the compiler emits a second, `gt`, compare for the max)
-__device__ __forceinline__ void cswap_u64(uint64_t& a, uint64_t& b) {
-  const uint64_t lt = __builtin_amdgcn_ballot_w64(a < b);
-  const uint32_t alo = (uint32_t)a, ahi = (uint32_t)(a >> 32), blo = (uint32_t)b,
-                 bhi = (uint32_t)(b >> 32);
-  a = ((uint64_t)sel_u32(lt, ahi, bhi) << 32) | sel_u32(lt, alo, blo);
-  b = ((uint64_t)sel_u32(lt, bhi, ahi) << 32) | sel_u32(lt, blo, alo);
-}
-
-// ascending sort of EPL u64 keys in registers (Batcher odd-even merge network)
-template <int EPL>
-__device__ __forceinline__ void sort_keys(uint64_t (&k)[EPL]) {
-  static_assert((EPL & (EPL - 1)) == 0, "EPL must be a power of two");
-#pragma unroll
-  for (int p = 1; p < EPL; p <<= 1)
-#pragma unroll
-    for (int q = p; q > 0; q >>= 1)
-#pragma unroll
-      for (int j = q % p; j + q < EPL; j += 2 * q)
-#pragma unroll
-        for (int i = 0; i < q; ++i)
-          if (i + j + q < EPL && (i + j) / (2 * p) == (i + j + q) / (2 * p)) {
-#if CO_SLAP_CSWAP
-            cswap_u64(k[i + j], k[i + j + q]);
-#else
-            const uint64_t a = k[i + j], b = k[i + j + q];
-            k[i + j] = a < b ? a : b;
-            k[i + j + q] = a < b ? b : a;
-#endif
-          }
 }
 
 // ----------------------------------------------------------------------------- SLAP
@@ -721,38 +585,13 @@ __host__ __device__ inline size_t slap_wave_bytes_sd(int gpw, int epl, int L, in
   return slap_xy_bytes(gpw, L) + ((area + 15) & ~(size_t)15);
 }
 
-#ifndef CO_SLAP_LATE
-#define CO_SLAP_LATE 0  // 1: the coordinates, 2: also the picklist loaded after the step loop
-#endif
-
-#ifndef CO_SLAP_POP
-#define CO_SLAP_POP 0  // 1: branch-free pop in the closest-free step loop (r05: 43.9 against 42.0 us)
-#endif
-
-#ifndef CO_SLAP_WPE
-#define CO_SLAP_WPE 0  // > 0: amdgpu_waves_per_eu floor (SGPRs cap the kernel at 7 waves)
-#endif
-#if CO_SLAP_WPE > 0
-#define CO_SLAP_ATTR __attribute__((amdgpu_waves_per_eu(CO_SLAP_WPE)))
-#else
-#define CO_SLAP_ATTR
-#endif
-
-#ifndef CO_SLAP_NT
-#define CO_SLAP_NT 0  // non-temporal loads / stores (r06: 47 -> 53 us at B = 65,536: partial-line
-                      // accesses; nt pays only for whole-line streams such as LDS-DMA)
-#endif
-
-#ifndef CO_SLAP_SD
-#define CO_SLAP_SD 1  // stage coordinates and depot distances by LDS-DMA (nt) when aligned
-                      // (r06: B = 16,384 18.9 -> 17.0 us, 65,536 48.0 -> 45.1 us, A/B)
-#endif
-#ifndef CO_SLAP_PNT
-#define CO_SLAP_PNT 0  // picklist loads non-temporal (r06: 44.8 -> 47.2 us at B = 65,536: off)
-#endif
+// A coordinate pair returned by value: one 8-byte load in the compiler's eyes (the plain
+// copy `xr[k] = lrow[c]` is two 4-byte member loads to it, and the SD = false kernels'
+// register allocation then differs from the measured code).
+__device__ __forceinline__ float2 ld_pair(const float2* p) { return *p; }
 
 template <int G, int EPL, bool CLOSEST, bool SD>
-__global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
+__global__ __launch_bounds__(256) void slap_group_kernel(
     int64_t B, int L, int P, int O, int K, const float2* __restrict__ locs,
     const int64_t* __restrict__ picklist, const float* __restrict__ depot_dist,
     const int32_t* __restrict__ assign_in, const int64_t* __restrict__ acts_in,
@@ -761,7 +600,6 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
     uint8_t* __restrict__ step_reward_out, float* __restrict__ reward_out,
     float* __restrict__ ratio_out, int32_t* status) {
   constexpr int IPB = 256 / G, GPW = 64 / G;
-  constexpr bool NT = CO_SLAP_NT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [IPB][P] assignment rows, then one region per wave that holds the sorted candidate
   // keys [EPL][64] during the step loop and, after it (same wave, program order), the
@@ -793,10 +631,7 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
   if constexpr (SD) {
     wave_dma<2>(reinterpret_cast<const unsigned char*>(depot_dist + wbase * L), wrows * L * 4,
                 area);
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_dma_wait();
   }
 
   // Loads are issued in the order they are needed: the depot distances (the step loop),
@@ -813,7 +648,7 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
     if constexpr (SD)
       dd[k] = (CLOSEST && ok) ? reinterpret_cast<const float*>(area)[gw * L + c] : __builtin_inff();
     else
-      dd[k] = (CLOSEST && ok) ? ld_s<NT>(depot_dist + bb * L + c) : __builtin_inff();
+      dd[k] = (CLOSEST && ok) ? (depot_dist + bb * L)[c] : __builtin_inff();
   }
   if constexpr (SD) {  // the coordinates stream in behind the sort and the step loop
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the distance reads are back
@@ -828,7 +663,7 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
       for (int c4 = sl; c4 < (L >> 2); c4 += G)
         *reinterpret_cast<float4*>(rrow + 4 * c4) = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
-      for (int c = sl; c < L; c += G) st_s<NT>(rrow + c, 0.f);
+      for (int c = sl; c < L; c += G) rrow[c] = 0.f;
     }
   }
   const float2* lrow = locs + bb * L;
@@ -838,12 +673,8 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
 #pragma unroll
   for (int k = 0; k < EPL; ++k) {
     const int c = sl + G * k;
-#if !CO_SLAP_LATE
-    if constexpr (!SD) xr[k] = c < L ? ld_s<NT>(lrow + c) : make_float2(0.f, 0.f);
-#endif
-#if CO_SLAP_LATE < 2
-    pr[k] = c < O * K ? ld_s<NT || CO_SLAP_PNT>(prow + c) : 0;
-#endif
+    if constexpr (!SD) xr[k] = c < L ? ld_pair(lrow + c) : make_float2(0.f, 0.f);
+    pr[k] = c < O * K ? prow[c] : 0;
   }
   // closest-free = the free locations in increasing (distance, index) order.  Each lane
   // sorts its EPL candidates once (keys: order-preserving u32 of the distance, then the
@@ -857,34 +688,15 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
     return (pp < 0 || pp >= P) ? -1 : (int32_t)pp;
   };
   int32_t pw[EPL];
-#if CO_SLAP_LATE < 2
 #pragma unroll
   for (int k = 0; k < EPL; ++k) pw[k] = wrap_product(pr[k]);
-#endif
   uint64_t key[EPL];
   if (CLOSEST) {
 #pragma unroll
-    for (int k = 0; k < EPL; ++k) {
-#if CO_SLAP_KEY2
-      // -0.0 keyed as +0.0 (d + 0.0 is +0.0 for d = -0.0, d otherwise): they tie as in
-      // argmin's float compare, and the index decides
-      const uint32_t u = __float_as_uint(dd[k] + 0.0f);
-      const uint32_t ord = u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
-#else
-      // -0.0 keyed as +0.0: they tie (argmin's float compare), the index decides
-      const uint32_t u = dd[k] == 0.f ? 0u : __float_as_uint(dd[k]);
-      const uint32_t ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-#endif
-      key[k] = ((uint64_t)ord << 32) | (uint32_t)(sl + G * k);
-    }
+    for (int k = 0; k < EPL; ++k)
+      key[k] = ((uint64_t)dist_key(dd[k]) << 32) | (uint32_t)(sl + G * k);
     sort_keys<EPL>(key);
   }
-#if defined(CO_SLAP_CUT) && CO_SLAP_CUT == 1
-  if (live && sl == 0 && (uint32_t)key[0] == 12345u + (uint32_t)pr[0] + (uint32_t)__float_as_uint(xr[0].x))
-    reward_out[bb] = 1.f;
-  return;
-#endif
-  constexpr uint32_t kOrdInf = 0xff800000u;  // ordered key of +inf
   bool range = false;
   if (CLOSEST) {
     // The lane's head and next key stay in registers, the rest of its sorted list in
@@ -895,59 +707,13 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
 #pragma unroll
     for (int k = 2; k < EPL; ++k) s_keys[k * 64 + lane] = key[k];
     int h = 2;
-#if CO_SLAP_POP
-    // branch-free pop: every lane reads the key after its `next` each step (issued before
-    // the two group reductions, so its latency hides behind them) and the owner's head /
-    // next / free bit move by selects -- no divergent branch and exec-mask juggling per step
-    for (int t = 0; t < P; ++t) {
-      const uint64_t nn = h < EPL ? s_keys[h * 64 + lane] : ~0ull;
-      const uint32_t hh = (uint32_t)(hk >> 32);
-      const uint32_t gm = grp_reduce<G>(hh, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
-      const uint32_t cand = hh == gm ? (uint32_t)hk : 0xffffffffu;
-      const uint32_t gi =
-          grp_reduce<G>(cand, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
-      const bool any = gm < kOrdInf;
-      const bool pop = any && (uint32_t)hk == gi;  // the owner's head is the chosen location
-      avail &= pop ? ~(1u << (gi / G)) : ~0u;
-      hk = pop ? nk : hk;
-      nk = pop ? nn : nk;
-      h += pop ? 1 : 0;
-      if (sl == 0) asg[t] = any ? (int32_t)gi : 0;  // product t
-    }
-#else
-#if CO_SLAP_OWNW
-    // r06: the owner of the chosen location writes assignment[t] in its pop (a step with no
-    // candidate leaves the pre-stored 0), and the popped keys' free bits are cleared after
-    // the loop from their slots -- 2 VALU and an exec switch fewer per step
-    for (int t = sl; t < P; t += G) asg[t] = 0;
-    uint32_t slots = 0;  // nibble j: the register slot (location / G) of sorted key j
-#pragma unroll
-    for (int j = 0; j < EPL && j < 8; ++j) slots |= (((uint32_t)key[j] - sl) / G) << (4 * j);
-    __builtin_amdgcn_wave_barrier();  // (one wave: the zeros land before any pop's write)
     for (int t = 0; t < P; ++t) {
       const uint32_t hh = (uint32_t)(hk >> 32);
       const uint32_t gm = grp_reduce<G>(hh, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
       const uint32_t cand = hh == gm ? (uint32_t)hk : 0xffffffffu;
       const uint32_t gi =
           grp_reduce<G>(cand, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
-      if (gm < kOrdInf && (uint32_t)hk == gi) {  // the owner's head is the chosen location
-        asg[t] = (int32_t)gi;  // product t
-        hk = nk;
-        nk = h < EPL ? s_keys[h * 64 + lane] : ~0ull;
-        ++h;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < EPL && j < 8; ++j)
-      if (j < h - 2) avail &= ~(1u << ((slots >> (4 * j)) & 15u));
-#else
-    for (int t = 0; t < P; ++t) {
-      const uint32_t hh = (uint32_t)(hk >> 32);
-      const uint32_t gm = grp_reduce<G>(hh, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
-      const uint32_t cand = hh == gm ? (uint32_t)hk : 0xffffffffu;
-      const uint32_t gi =
-          grp_reduce<G>(cand, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
-      const bool any = gm < kOrdInf;
+      const bool any = gm < kDistKeyInf;
       if (any && (uint32_t)hk == gi) {  // the owner's head is the chosen location
         avail &= ~(1u << (gi / G));
         hk = nk;
@@ -956,8 +722,6 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
       }
       if (sl == 0) asg[t] = any ? (int32_t)gi : 0;  // product t
     }
-#endif
-#endif
   } else {
     // teacher actions: lane sl loads steps t = sl, sl + G, ... (all loads in flight at
     // once, a few VGPRs), writes the int32 assignment entry and the wrapped location (-1
@@ -995,42 +759,22 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
       }
     }
   }
-#if defined(CO_SLAP_CUT) && CO_SLAP_CUT == 2
-  {
-    uint32_t sink = avail;
-#pragma unroll
-    for (int k = 0; k < EPL; ++k)
-      sink += (uint32_t)pw[k] + __float_as_uint(xr[k].x) + __float_as_uint(xr[k].y);
-    if (live && sink == 12345u) reward_out[bb] = 1.f;
-    return;
-  }
-#endif
   if constexpr (SD) {  // the DMA'd coordinates have landed in place
     __builtin_amdgcn_s_waitcnt(0);
   } else {
 #pragma unroll
     for (int k = 0; k < EPL; ++k) {
       const int c = sl + G * k;
-#if CO_SLAP_LATE
-      xr[k] = c < L ? lrow[c] : make_float2(0.f, 0.f);
-#endif
       if (c < L) xy[c] = xr[k];
     }
   }
   // picklist entries as wrapped product indices (-1 = out of range)
-#if CO_SLAP_LATE >= 2
-#pragma unroll
-  for (int k = 0; k < EPL; ++k) {
-    const int c = sl + G * k;
-    pw[k] = c < O * K ? wrap_product(prow[c]) : 0;
-  }
-#endif
 #pragma unroll
   for (int k = 0; k < EPL; ++k) {  // entry sl + G*k is register pw[k]
     const int c = sl + G * k;
     if (c < O * K) pks[c] = (int16_t)pw[k];
   }
-  for (int c = sl + G * EPL; c < O * K; c += G) pks[c] = (int16_t)wrap_product(ld_s<NT>(prow + c));
+  for (int c = sl + G * EPL; c < O * K; c += G) pks[c] = (int16_t)wrap_product(prow[c]);
   // the group's LDS rows are written and read by lanes of the same wave: a wave-level
   // fence orders them, no workgroup barrier (groups do not wait for other waves)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1046,7 +790,12 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
     for (int idx = lane; idx < IPW * P; idx += 64) {
       const int t = idx / IPW, gi = idx - t * IPW;
       const int64_t be = (int64_t)blockIdx.x * IPB + w0 + gi;
-      if (be < B) st_s<NT>(acts_out + (int64_t)t * B + be, (int64_t)s_asg[(w0 + gi) * P + t]);
+      if (be < B) {
+        // (here and below: the address formed before the value is read, the order the
+        // measured machine code was compiled from)
+        int64_t* dst = acts_out + (int64_t)t * B + be;
+        *dst = (int64_t)s_asg[(w0 + gi) * P + t];
+      }
     }
   }
   // one lane per order; for K <= 8 the K picks' LDS lookups (product -> location ->
@@ -1077,10 +826,6 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-#if defined(CO_SLAP_CUT) && CO_SLAP_CUT == 3
-  if (live && sl == 0) reward_out[bb] = olen[0] + (float)avail;
-  return;
-#endif
   if (live) {
     uint8_t* mrow = mask_out + bb * L;
     if (((reinterpret_cast<uintptr_t>(mask_out) | (uintptr_t)L) & 3) == 0) {
@@ -1102,7 +847,10 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
 #pragma unroll
       for (int k = 0; k < EPL; ++k) {
         const int c = sl + G * k;
-        if (c < L) st_s<NT>(mrow + c, (uint8_t)((avail >> k) & 1u));
+        if (c < L) {
+          uint8_t* dst = mrow + c;
+          *dst = (uint8_t)((avail >> k) & 1u);
+        }
       }
     }
     if (((reinterpret_cast<uintptr_t>(assign_out) | ((uintptr_t)P * 4)) & 15) == 0) {
@@ -1112,7 +860,10 @@ __global__ __launch_bounds__(256) CO_SLAP_ATTR void slap_group_kernel(
     } else {
       // (not unrolled: the compiler's 16-way unroll of this loop set the kernel's VGPR peak)
 #pragma unroll 2
-      for (int c = sl; c < P; c += G) st_s<NT>(assign_out + bb * P + c, asg[c]);
+      for (int c = sl; c < P; c += G) {
+        int32_t* dst = assign_out + bb * P + c;
+        *dst = asg[c];
+      }
     }
     if (sl == 0) {
       // f32 order-by-order accumulation of slap/env.py:135-142 (four lengths per LDS read
@@ -1143,31 +894,23 @@ int launch_tsp_teacher(int64_t B, int64_t N, const float2* l2, int64_t LB, const
                        uint8_t* mask_out, int64_t* first_out, int64_t* cur_out, int64_t* i_out,
                        uint8_t* done_out, uint8_t* step_reward_out, float* reward_out, int check,
                        int32_t* status, hipStream_t s) {
-  constexpr int Q = CO_TEACH_Q, PRE = CO_TEACH_NB;
+  constexpr int Q = CO_TEACH_Q;
   const int NW = NW_launch(N);
   const size_t shmem = tsp_tile_bytes((int)N, Q) + (size_t)64 * (2 * NW + 1) * 4;
   const dim3 grid(cover_grid(B, 64, 64 * Q)), block(64 * Q);
   if (grid.x == 0) return CO_E_INVAL;
-  // a wave's step range fits the register prefetch: R = ceil((N - 1) / Q) <= PRE * U
-  const bool pre = PRE > 0 && (N - 1 + Q - 1) / Q <= PRE * CO_TEACH_U;
-#define CO_TEACH(W, P)                                                                         \
+#define CO_TEACH(W)                                                                            \
   do {                                                                                         \
     if (shmem > 64 * 1024)                                                                     \
-      (void)hipFuncSetAttribute((const void*)tsp_teacher_kernel<W, Q, STATE, P>,               \
+      (void)hipFuncSetAttribute((const void*)tsp_teacher_kernel<W, Q, STATE, 0>,               \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);       \
-    hipLaunchKernelGGL((tsp_teacher_kernel<W, Q, STATE, P>), grid, block, shmem, s, B, (int)N, \
+    hipLaunchKernelGGL((tsp_teacher_kernel<W, Q, STATE, 0>), grid, block, shmem, s, B, (int)N, \
                        l2, LB, acts, mask_out, first_out, cur_out, i_out, done_out,                \
                        step_reward_out, reward_out, check, status);                            \
   } while (0)
-  if (NW == 1) {
-    if (pre) CO_TEACH(1, PRE);
-    else CO_TEACH(1, 0);
-  } else if (NW == 2) {
-    if (pre) CO_TEACH(2, PRE);
-    else CO_TEACH(2, 0);
-  } else {
-    CO_TEACH(4, 0);
-  }
+  if (NW == 1) CO_TEACH(1);
+  else if (NW == 2) CO_TEACH(2);
+  else CO_TEACH(4);
 #undef CO_TEACH
   return launch_status();
 }
@@ -1180,7 +923,7 @@ int launch_tsp_rows(int64_t B, int64_t N, const float2* l2, int64_t LB, const in
   const bool vec = ((reinterpret_cast<uintptr_t>(acts) & 15) == 0) && (sb % 2 == 0);
   // LDS-DMA staging: contiguous rows (sb == N), 16-byte aligned blocks (the wave's GPW rows
   // start at a multiple of 32N bytes), the multistart row map not wrapping inside a wave
-  const bool dma_ok = CO_ROWS_DMA && sb == N &&
+  const bool dma_ok = sb == N &&
                       ((reinterpret_cast<uintptr_t>(acts) | reinterpret_cast<uintptr_t>(l2)) & 15) == 0;
 #define CO_ROWS(GG, EE)                                                                        \
   do {                                                                                         \
@@ -1190,13 +933,8 @@ int launch_tsp_rows(int64_t B, int64_t N, const float2* l2, int64_t LB, const in
     const size_t dsh = WPB * tsp_rows_wave_bytes(64 / GG, (int)N);                             \
     /* the static visited bitmaps come on top of the dynamic staging (64 KiB default) */       \
     const size_t sbits = (size_t)WPB * (64 / GG) * ((GG * EE + 31) / 32) * 4;                  \
-    if (CO_ROWS_MODE3 && dma_ok && (LB == B || LB % (64 / GG) == 0) &&                       \
-        dsh / 2 + sbits <= 64 * 1024)                                                          \
-      hipLaunchKernelGGL((tsp_teacher_rows_kernel<GG, EE, 3, STATE>), grid, block, dsh / 2, s,  \
-                         B, (int)N, l2, LB, acts, sb, mask_out, first_out, cur_out, i_out,     \
-                         done_out, step_reward_out, reward_out, check, status);                \
-    else if (dma_ok && (LB == B || LB % (64 / GG) == 0) && dsh + sbits <= 64 * 1024)           \
-      hipLaunchKernelGGL((tsp_teacher_rows_kernel<GG, EE, 2, STATE>), grid, block, dsh, s, B,   \
+    if (dma_ok && (LB == B || LB % (64 / GG) == 0) && dsh + sbits <= 64 * 1024)                \
+      hipLaunchKernelGGL((tsp_teacher_rows_kernel<GG, EE, 3, STATE>), grid, block, dsh, s, B,   \
                          (int)N, l2, LB, acts, sb, mask_out, first_out, cur_out, i_out,        \
                          done_out, step_reward_out, reward_out, check, status);                \
     else if (vec)                                                                              \
@@ -1337,7 +1075,7 @@ extern "C" int co_slap_rollout(int64_t B, int64_t L, int64_t P, int64_t O, int64
   const int G = L <= 64 ? 8 : (L <= 128 ? 16 : 32);
   const int ipb = 256 / G;
   // LDS-DMA staging of the distance / coordinate rows: 16-byte aligned row blocks
-  const bool sd = CO_SLAP_SD && closest && (L % 4) == 0 &&
+  const bool sd = closest && (L % 4) == 0 &&
                   ((reinterpret_cast<uintptr_t>(locs) | reinterpret_cast<uintptr_t>(depot_dist)) &
                    15) == 0;
   const size_t shmem =

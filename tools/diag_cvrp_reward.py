@@ -1,6 +1,6 @@
 """Time co_cvrp_reward alone (diagnostic): the stepwise CVRP-100 episode's step-major
 actions at B=32768, 30 launches, HIP events; with and without the validity check.
-CO_LIB selects a variant library (tools/build_variants.sh, e.g. -DCO_CVRP_RCUT=1)."""
+CO_LIB selects a variant library (tools/build_variants.sh) for a same-box A/B."""
 import json
 import os
 import sys
@@ -61,14 +61,3 @@ torch.cuda.synchronize(dev)
 out["rowmajor_check1_us"] = e0.elapsed_time(e1) * 1e3 / 30
 out["rowmajor_close"] = bool(torch.allclose(rew_rm, ref, rtol=1e-6, atol=0)) and int(ep.status.item()) == 0
 print(json.dumps(out))
-if os.environ.get("CO_TIMING"):  # a -DCO_CVRPR_TIMING build: per-workgroup phase clocks
-    f = nat.bind("co_cvrp_reward", b, n, T, nat.ptr(ep.locs), nat.ptr(acts), 1, b,
-                 nat.ptr(ep.demand), nat.ptr(ep.vcap_t), 1, nat.ptr(ep.reward),
-                 nat.ptr(ep.status))
-    f(s)
-    f(s)
-    torch.cuda.synchronize(dev)
-    tm = ep.reward.view(-1, 64)[:, :5].cpu().double()
-    names = ["start", "staged", "scanner_done", "walkers_done", "end"]
-    print(json.dumps({nm: [round(float(tm[:, i].quantile(p)), 0) for p in (0.1, 0.5, 0.9, 1.0)]
-                      for i, nm in enumerate(names)}))

@@ -1,6 +1,6 @@
 """Time co_cvrp_step alone (diagnostic): B=32768 CVRP-100 state after a few nearest-policy
 steps, 50 launches on fixed inputs, HIP events.  CO_LIB selects a variant library
-(tools/build_variants.sh, e.g. the CO_CVRP_CUT timing cuts)."""
+(tools/build_variants.sh) for a same-box A/B."""
 import json
 import os
 import sys
