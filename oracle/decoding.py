@@ -68,6 +68,82 @@ def sampling(logprobs, mask=None, generator=None):  # decoding.py:383-397
     return sel
 
 
+def decode_draw_u(batch, seed, offset, row0=0):
+    """The decode step's uniform draw of rows ``row0 .. row0 + batch - 1`` (include/co_env.h,
+    csrc/decode_common.hpp: not torch's generator): ``u = (w >> 8) * 2^-24`` with ``w`` word
+    0 of Philox-4x32-10 under key ``(seed_lo, seed_hi)`` at counter ``(offset_lo, offset_hi,
+    row_lo, row_hi)``.  float64 (every value is on the f32 grid)."""
+    import numpy as np
+
+    from .generate import MASK, philox4x32_10
+
+    rows = [(row0 + i) & 0xFFFFFFFFFFFFFFFF for i in range(batch)]
+    ctr = np.empty((batch, 4), dtype=np.uint64)
+    ctr[:, 0] = offset & MASK
+    ctr[:, 1] = (offset >> 32) & MASK
+    ctr[:, 2] = [r & MASK for r in rows]
+    ctr[:, 3] = [r >> 32 for r in rows]
+    key = np.array([[seed & MASK, (seed >> 32) & MASK]], dtype=np.uint64)
+    w = philox4x32_10(ctr, key)[:, 0]
+    return torch.from_numpy((w >> np.uint64(8)).astype(np.float64) * 2.0 ** -24)
+
+
+def sample_inverse_cdf(logp, u):
+    """The sampled action as a function of the draw, in float64: with ``p = exp(logp)`` and
+    ``cdf = p.cumsum(-1) / p.sum(-1)``, the first index with ``p > 0`` and ``cdf > u``; the
+    last index with ``p > 0`` when there is none.  Returns ``(action[B], margin[B])``,
+    ``margin = min_c |cdf[c] - u|``: an f32 evaluation whose running sums are within
+    ``margin`` of these picks the same action."""
+    p = logp.double().exp()
+    cdf = p.cumsum(-1)
+    cdf = cdf / cdf[..., -1:]
+    u = u.double().reshape(-1, 1)
+    n = p.shape[-1]
+    idx = torch.arange(n).expand_as(p)
+    pos = p > 0
+    hit = torch.where(pos & (cdf > u), idx, torch.full_like(idx, n)).min(-1).values
+    last = torch.where(pos, idx, torch.full_like(idx, -1)).max(-1).values
+    action = torch.where(hit < n, hit, last.clamp(min=0))
+    margin = (cdf - u).abs().min(-1).values
+    return action, margin
+
+
+def sample_margin_tol(n):
+    """How far an f32 inverse CDF of a row of ``n`` may be from ``sample_inverse_cdf``'s,
+    in units of the total: the rounding of the longest chain of f32 additions into any
+    running sum (short rows, ``n <= 2048``: the max(8, n/64) elements of a lane, then the
+    6 steps of the scan; long rows: the n/256 block carries, the 6 scan steps and the 3
+    wave totals), one ulp of ``expf`` per term, the rounding of the total and that of
+    ``u * total`` -- each at most 2^-24 of a sum that is at most the total -- times a
+    slack factor 4."""
+    import math
+
+    if n > 2048:
+        return 4 * (math.ceil(n / 256) + 12) * 2.0 ** -24
+    return 4 * (max(8, math.ceil(n / 64)) + 9) * 2.0 ** -24
+
+
+def beam_rank(logp, parent, beam_width):
+    """``decoding.py:611-641`` for one step, ties by candidate index: ``logp`` ``[BW*B, N]``
+    and ``parent`` ``[BW*B]`` in the ``s*B + b`` row layout; instance ``b``'s candidate
+    ``t = s*N + c`` scores ``logp[s*B + b, c] + parent[s*B + b]`` (f32 add); the ``BW`` best
+    by a stable descending sort (equal scores: the lower ``t``; NaN ranks greatest, as in
+    ``torch.topk``).  Returns ``(selected, beam_parent, beam_row, score)``, each ``[BW*B]``
+    with rank ``j`` of instance ``b`` at row ``j*B + b``."""
+    e, n = logp.shape
+    b = e // beam_width
+    score = logp.float() + parent.float().reshape(e, 1)
+    hst = torch.cat(score.split(b), dim=1)  # [B, BW*N], column s*N + c
+    vals, order = torch.sort(hst, dim=1, descending=True, stable=True)
+    topv, topi = vals[:, :beam_width], order[:, :beam_width]
+    flat = lambda t: torch.hstack(torch.unbind(t, 1))  # noqa: E731  ([B, BW] -> j*B + b)
+    topv, topi = flat(topv), flat(topi)
+    selected = topi % n
+    beam_parent = (topi // n).int()
+    beam_row = torch.arange(b).repeat(beam_width) + beam_parent.long() * b
+    return selected, beam_parent, beam_row, topv
+
+
 def get_log_likelihood(logprobs, actions=None, mask=None, return_sum=True):  # decoding.py:39-65
     if actions is not None and logprobs.dim() == 3:
         logprobs = logprobs.gather(-1, actions.unsqueeze(-1)).squeeze(-1)
@@ -170,15 +246,16 @@ class BeamSearchOracle:
         logp = process_logits(logits, m, self.temperature, self.tanh_clipping, self.mask_logits)
         e, n = logp.shape
         b = e // self.beam_width
-        seq = torch.arange(0, b).repeat(self.beam_width)
         hst = torch.cat((logp + self.parent_beam_logprobs).split(b), dim=1)
-        topv, topi = torch.topk(hst, self.beam_width, dim=1)
-        sel_lp = torch.hstack(torch.unbind(topv, 1)).unsqueeze(1)
-        topi = torch.hstack(torch.unbind(topi, 1))
-        selected = topi % n
-        parent = (topi // n).int()
-        idx = seq + parent * b
-        self.parent_beam_logprobs = sel_lp
+        topv, _ = torch.topk(hst, self.beam_width, dim=1)
+        # torch.topk leaves the order of equal scores unspecified, and f32 sums of many
+        # log-probabilities do collide (BW = 120 beams of TSP-140: several exact ties per
+        # step): the candidates are ranked by beam_rank's stable sort (equal scores -> the
+        # lower s*N + c, include/co_env.h); the ranked values must be topk's
+        selected, parent, idx, sel_lp = beam_rank(logp, self.parent_beam_logprobs, self.beam_width)
+        assert torch.equal(sel_lp.view(torch.int32),
+                           torch.hstack(torch.unbind(topv, 1)).view(torch.int32))
+        self.parent_beam_logprobs = sel_lp.unsqueeze(1)
         self.beam_path.append(parent)
         td = self._rows(td, idx)
         logp = logp[idx]
@@ -212,4 +289,5 @@ class BeamSearchOracle:
 
 
 __all__ = ["process_logits", "greedy", "sampling", "get_log_likelihood", "Decoding",
-           "BeamSearchOracle", "batchify"]
+           "BeamSearchOracle", "batchify", "decode_draw_u", "sample_inverse_cdf",
+           "sample_margin_tol", "beam_rank"]

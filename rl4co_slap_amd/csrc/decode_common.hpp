@@ -1005,8 +1005,14 @@ __global__ __launch_bounds__(256) void tsp_decode_greedy_kernel(
 // accumulator chains of map_reduce_all walked over 1,024-element LDS chunks by 16
 // threads, the xor-8/4/2/1 butterfly; correctly rounded tanh).  Greedy = first index of
 // the maximal logp (as GreedyRow::select), evaluate, sampling = inverse CDF over the row
-// in index order (statistical parity, like the short rows: a different summation order
-// than DecodeRow's lane layout), top-k by level peeling.  top-p is not offered here.
+// in index order, top-k by level peeling.  top-p is not offered here.
+// Sampling, here and in DecodeRow, is a deterministic function of the row: the first
+// column with p > 0 whose running sum of p = exp(logp) passes u * total, u the Philox draw
+// of (seed, offset, global row).  Only the order of the f32 additions differs between
+// this kernel, DecodeRow's lane layouts and the host build, so all three pick the action
+// of the float64 inverse CDF on every row whose u is further from each step of that CDF
+// than the rounding of the sums (oracle.decoding.sample_margin_tol; pinned per bucket,
+// load path and option by tests/test_gpu_sampling_exact.py and tests/test_host_sampling.py).
 namespace {
 
 constexpr int kLongThreads = 256, kLongChunk = 1024;

@@ -86,7 +86,7 @@ extern "C" int co_decode_step(int64_t B, int64_t N, const float* logits, int64_t
 // BeamSearch._make_beam_step (decoding.py:611-641) + the feasibility assert of _step
 // (:512-524): for instance b, candidate t = s*N + c (beam s, node c) scores
 // logp[s*B + b, c] + parent[s*B + b] (f32 add, as the reference's broadcast add); the
-// BW best (torch.topk, sorted; equal scores -> lower t) go to rows j*B + b:
+// BW best (torch.topk, sorted; equal scores -> lower t; NaN ranks greatest) go to rows j*B + b:
 // selected = t % N, beam_parent = t / N, beam row = b + beam_parent*B, new parent score.
 // One wave per instance: the BW*N scores are staged in LDS, then BW rounds of a wave
 // argmax over the untaken ones (a taken bitmap in LDS).
@@ -116,7 +116,10 @@ __global__ __launch_bounds__(64) void beam_select_kernel(
       for (int t = lane; t < T; t += 64) {
         const bool free_t = !((taken[t >> 5] >> (t & 31)) & 1u);
         const float v = sc[t];
-        if (free_t && (v > bv || (v == bv && t < bi) || bi == 0x7fffffff)) {
+        // the wave step's order (a NaN score ranks greatest, as in torch.topk); the lane's
+        // first free element is taken whatever its value, so a lane of -inf scores still
+        // offers its lowest free index
+        if (free_t && (bi == 0x7fffffff || argmax_better(v, t, bv, bi))) {
           bv = v;
           bi = t;
         }

@@ -1,7 +1,8 @@
 """The two builds of the C ABI against each other: the host library (CPU TensorDicts,
 csrc/host) and the gfx950 library on identical inputs through the same env classes --
 every step's state bit-equal, rewards within 1e-5, decode log-probabilities bit-equal
-(both restate ATen's F.log_softmax), greedy actions equal."""
+(both restate ATen's F.log_softmax), greedy actions equal, sampled actions equal outside
+the rounding margin of the inverse CDF."""
 import numpy as np
 import pytest
 import torch
@@ -76,3 +77,34 @@ def test_decode_host_equals_device(dev, n, clip, temp):
     assert torch.equal(ah, ad.cpu())
     assert torch.equal(lh, ld.cpu())
     assert torch.equal(fh, fd.cpu())
+
+
+@pytest.mark.parametrize("n", [10, 37, 100, 200, 1025, 2049])
+@pytest.mark.parametrize("clip,temp", [(0.0, 1.0), (10.0, 1.0), (10.0, 0.8)])
+def test_decode_sampling_host_equals_device(dev, n, clip, temp):
+    """Sampling: both builds draw the same u per (seed, offset, row) and invert the same
+    CDF, summed in different orders -- equal actions on every row whose draw is further
+    than sample_margin_tol(N) from each step of the CDF (oracle.decoding, the margin of
+    tests/test_gpu_sampling_exact.py), and the same logp bits wherever the actions agree."""
+    from oracle import decoding as odec
+
+    b = 300
+    seed, offset = 0x0FEDCBA987654321, 2 ** 32 + 7
+    g = torch.Generator().manual_seed(n)
+    x = torch.randn(b, n, generator=g) * (4 if n <= 2048 else 1.5)
+    mask = torch.rand(b, n, generator=g) > 0.25
+    mask[:, -1] = True
+    ah, lh, fh = decode_step(x, mask, "sampling", temp, clip, return_full=True, seed=seed,
+                             offset=offset)
+    ad, ld, fd = decode_step(x.to(dev), mask.to(dev), "sampling", temp, clip, return_full=True,
+                             seed=seed, offset=offset)
+    ad, ld = ad.cpu(), ld.cpu()
+    assert torch.equal(fh, fd.cpu())
+    _, margin = odec.sample_inverse_cdf(fh, odec.decode_draw_u(b, seed, offset))
+    rows = margin > odec.sample_margin_tol(n)
+    skipped = b - int(rows.sum())
+    assert skipped <= 0.05 * b, skipped
+    assert torch.equal(ah[rows], ad[rows]), f"{skipped} rows left out within the margin"
+    same = ah == ad
+    assert torch.equal(lh[same].view(torch.int32), ld[same].view(torch.int32))
+    assert torch.equal(lh, fh.gather(1, ah[:, None]).squeeze(1))

@@ -72,7 +72,9 @@ def test_policy_evaluate_and_sampling_consistency(dev):
     assert torch.allclose(ev["log_likelihood"], smp["log_likelihood"], rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("name,b,n,bw", [("tsp", 8, 10, 4), ("tsp", 5, 20, 20), ("cvrp", 6, 12, 3)])
+# ("tsp", 2, 140, 120): BW*N = 16,800 scores, past 64 KB of LDS (co_beam_select's large launch)
+@pytest.mark.parametrize("name,b,n,bw", [("tsp", 8, 10, 4), ("tsp", 5, 20, 20), ("cvrp", 6, 12, 3),
+                                         ("tsp", 2, 140, 120)])
 @pytest.mark.parametrize("select_best", [True, False])
 def test_policy_beam_search_matches_oracle(dev, name, b, n, bw, select_best):
     ref_env, td_ref, env, td = _pair(name, b, n, 300 + n, dev)

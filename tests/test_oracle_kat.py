@@ -167,6 +167,60 @@ def test_philox_known_answers(ctr, key, want):
     assert tuple(int(v) for v in got[0]) == want
 
 
+@pytest.mark.parametrize("ctr,key,want", PHILOX_KAT)
+def test_decode_draw_counter_layout_known_answers(ctr, key, want):
+    """The decode step's draw (oracle.decoding.decode_draw_u) on the published vectors:
+    counter = (offset_lo, offset_hi, row_lo, row_hi), key = (seed_lo, seed_hi), the draw
+    is the top 24 bits of output word 0.  The third vector has six distinct input words,
+    so any other placement of the halves gives another value."""
+    from oracle.decoding import decode_draw_u
+
+    seed = key[0] | (key[1] << 32)
+    offset = ctr[0] | (ctr[1] << 32)
+    row = ctr[2] | (ctr[3] << 32)
+    u = decode_draw_u(1, seed, offset, row0=row)
+    assert u.dtype == torch.float64 and u.shape == (1,)
+    assert u.item() == (want[0] >> 8) * 2.0 ** -24
+    if row < 2 ** 64 - 2:  # consecutive rows step counter word 2 (with carry into word 3)
+        from oracle.generate import philox4x32_10
+
+        nxt = row + 2
+        w = philox4x32_10(np.array([[ctr[0], ctr[1], nxt & 0xFFFFFFFF, nxt >> 32]], dtype=np.uint64),
+                          np.array([key], dtype=np.uint64))[0, 0]
+        assert decode_draw_u(3, seed, offset, row0=row)[2].item() == (int(w) >> 8) * 2.0 ** -24
+
+
+def test_sample_inverse_cdf_and_beam_rank_hand_cases():
+    """Hand-worked cases of the two decode references (no library involved)."""
+    from oracle.decoding import beam_rank, sample_inverse_cdf
+
+    p = torch.tensor([[0.25, 0.0, 0.5, 0.25, 0.0]] * 5)
+    u = torch.tensor([0.0, 0.2, 0.3, 0.76, 0.999], dtype=torch.float64)
+    a, m = sample_inverse_cdf(p.log(), u)
+    # cdf = .25 .25 .75 1 1 (to the f32 rounding of log p): the first column whose cdf
+    # passes u; zero-probability columns (same cdf as their predecessor) are never picked
+    assert a.tolist() == [0, 0, 2, 3, 3]
+    assert torch.allclose(m, torch.tensor([0.25, 0.05, 0.05, 0.01, 0.001], dtype=torch.float64),
+                          atol=1e-6)
+    # u on a step of the cdf (exact in float64): the comparison is strict, margin 0
+    a, m = sample_inverse_cdf(torch.tensor([[0.5, 0.0, 0.5]], dtype=torch.float64).log(),
+                              torch.tensor([0.5]))
+    assert a.tolist() == [2] and m.item() == 0.0
+    # no cdf above u (u = 1 is off the draw's grid): the last positive column
+    assert sample_inverse_cdf(p[:1].log(), torch.tensor([1.0]))[0].tolist() == [3]
+    # B = 2, BW = 2, N = 3; rows s*B + b.  Instance 0: beam 0 scores (-1, -2, -inf) + 0,
+    # beam 1 (-1, -3, -1) + 0 -> ties at -1 by t: t = 0, then t = 3.  Instance 1: a NaN
+    # first, then the best finite one.
+    ninf, nan = float("-inf"), float("nan")
+    logp = torch.tensor([[-1.0, -2.0, ninf], [-0.5, -0.25, -4.0],
+                         [-1.0, -3.0, -1.0], [-2.0, nan, -1.0]])
+    parent = torch.tensor([0.0, -1.0, 0.0, 0.5])
+    sel, par, row, sc = beam_rank(logp, parent, 2)
+    assert sel.tolist() == [0, 1, 0, 2] and par.tolist() == [0, 1, 1, 1]
+    assert row.tolist() == [0, 3, 2, 3]
+    assert sc[0] == -1.0 and sc[2] == -1.0 and torch.isnan(sc[1]) and sc[3] == -0.5
+
+
 def test_uniform_fill_oracle_grid_and_demand():
     from oracle.generate import uniform_fill
 
