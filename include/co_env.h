@@ -95,6 +95,33 @@ int co_tsp_reward(int64_t batch, int64_t num_loc, int64_t steps, const float* lo
                   int64_t locs_batch, const int64_t* actions, int64_t act_stride_b, int64_t act_stride_t, int check,
                   float* reward, int32_t* status, void* stream);
 
+/* TSPEnv.local_search (tsp/env.py:192-197 -> tsp/local_search.py:14-74): best-improvement
+ * 2-opt on every row, the whole search of a row in one launch.  Per sweep every move
+ * (i, j), 1 <= i < j <= n-1 (n = num_loc tour positions), is scored in f32, left to right,
+ *   change = ((D[t[i-1],t[j]] + D[t[i],t[(j+1)%n]]) - D[t[i-1],t[i]]) - D[t[j],t[(j+1)%n]]
+ * the smallest change (equal values: the lexicographically first (i, j)) is taken, and
+ * when it is < -1e-6 (compared in double) t[i..j] is reversed; the search ends with the
+ * first sweep that does not improve or after max_iterations sweeps.
+ * D (row = first operand) is distances[b % locs_batch] (f32 [locs_batch, n, n]) or, with
+ * locs (f32 [locs_batch, n, 2]), the f32 Euclidean sqrt(dx*dx + dy*dy) co_distance_matrix
+ * writes; exactly one of locs / distances is non-NULL.  actions element (b, k) lives at
+ * actions[b*act_stride_b + k*act_stride_t] (row-major or step-major, as co_tsp_reward).
+ * actions_out[batch, n] (row-major; must not alias actions) receives the improved tours,
+ * sweeps_out[batch] (nullable) the sweeps executed (the reference's `iterations`).
+ * max_iterations <= 0 copies the input (0 sweeps), n < 3 has no move (the input after 1
+ * sweep); max_iterations above 2^31 - 1 counts as 2^31 - 1.  A row that is not a
+ * permutation of 0..n-1 sets CO_ST_INVALID_TOUR and is copied unchanged with 0 sweeps (the
+ * reference has no such check: its uint16 cast and skip test leave such rows
+ * unspecified).  num_loc <= CO_TWO_OPT_MAX_N, else
+ * CO_E_INVAL.  One wavefront per row, tour state in LDS; a distances matrix of
+ * n <= CO_TWO_OPT_STAGE_N is staged in LDS, larger ones are read through L2. */
+#define CO_TWO_OPT_MAX_N 1024
+#define CO_TWO_OPT_STAGE_N 126
+int co_tsp_two_opt(int64_t batch, int64_t num_loc, const float* locs, const float* distances,
+                   int64_t locs_batch, const int64_t* actions, int64_t act_stride_b,
+                   int64_t act_stride_t, int64_t max_iterations, int64_t* actions_out,
+                   int32_t* sweeps_out, int32_t* status, void* stream);
+
 /* ----------------------------------------------------------------- CVRP */
 
 /* CVRPEnv._reset + get_action_mask (cvrp/env.py:107-149).  N = customers.

@@ -32,6 +32,7 @@ _SIGS = {
     "co_slap_closest_steps": [_i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p,
                               _i64, _p, _p, _p, _p],
     "co_tsp_reward": [_i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _p],
+    "co_tsp_two_opt": [_i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _p],
     "co_cvrp_reset": [_i64, _i64, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _p, _p],
     "co_cvrp_step": [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "co_cvrp_action_mask": [_i64, _i64, _p, _p, _p, _p, _p, _p, _p],
@@ -87,6 +88,8 @@ ST_TRUNCATED = 16
 ST_LOGP_NEG_INF = 32
 DECODE_FAST = 0x100  # CO_DECODE_FAST mode flag (opt-in fast math; not bit-exact)
 DECODE_CERTIFIED = 0x200  # CO_DECODE_CERTIFIED: fast math, greedy actions certified exact
+TWO_OPT_MAX_N = 1024  # CO_TWO_OPT_MAX_N: the longest tour co_tsp_two_opt takes
+TWO_OPT_STAGE_N = 126 # CO_TWO_OPT_STAGE_N: distance matrices up to this N are staged in LDS
 
 _lock = threading.Lock()
 _lib = None
@@ -137,7 +140,8 @@ def load():
 HOST_LIB_PATH = os.path.join(_HERE, "_lib", "libco_env_host.so")
 _host = None
 # the host (CPU) library exports the env / decode subset of the C ABI (csrc/host)
-HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_any_eq_i64",
+HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt",
+                "co_any_eq_i64",
                 "co_cvrp_reset", "co_cvrp_step", "co_cvrp_action_mask", "co_cvrp_reward",
                 "co_slap_reset", "co_slap_step", "co_slap_reward", "co_gather_by_index",
                 "co_decode_step"]

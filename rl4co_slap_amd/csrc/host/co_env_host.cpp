@@ -14,6 +14,7 @@
 // variants) and vec::map_reduce_all's 16-lane summation order, the same restatement as
 // csrc/co_math.hpp; tanh clipping is the correctly rounded tanh (f64 evaluation, one
 // rounding), as on the device.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -242,6 +243,75 @@ CO_HOST_API int co_tsp_reward(int64_t B, int64_t N, int64_t T, const float* locs
       len += edge_len(lr[2 * prev], lr[2 * prev + 1], lr[2 * first], lr[2 * first + 1]);
     reward[b] = -(float)len;
     if (check && bad) set_status(status, CO_ST_INVALID_TOUR);
+  }
+  return CO_OK;
+}
+
+// tsp/env.py:192-197 -> tsp/local_search.py:14-74: best-improvement 2-opt, the reference's
+// scalar double loop per row (one move per sweep; strict `<` from delta = 0 in ascending
+// (i, j) order, so equal changes keep the first; the -1e-6 tests in double)
+CO_HOST_API int co_tsp_two_opt(int64_t B, int64_t N, const float* locs, const float* distances,
+                               int64_t LB, const int64_t* actions, int64_t sb, int64_t st,
+                               int64_t max_iterations, int64_t* actions_out,
+                               int32_t* sweeps_out, int32_t* status, void*) {
+  if (B < 0 || N <= 0 || N > CO_TWO_OPT_MAX_N) return CO_E_INVAL;
+  if (LB <= 0 || (B > 0 && B % LB != 0)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if ((locs == nullptr) == (distances == nullptr)) return CO_E_INVAL;
+  if (!actions || !actions_out || actions_out == actions || !status) return CO_E_INVAL;
+  const int64_t n = N;
+  const int64_t max_it = max_iterations > INT32_MAX ? INT32_MAX : max_iterations;
+  std::vector<int64_t> tour((size_t)n);
+  std::vector<uint8_t> seen((size_t)n);
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t* ar = actions + b * sb;
+    int64_t* out = actions_out + b * n;
+    std::fill(seen.begin(), seen.end(), 0);
+    bool bad = false;
+    for (int64_t k = 0; k < n; ++k) {
+      const int64_t a = ar[k * st];
+      out[k] = a;
+      tour[(size_t)k] = a;
+      if (a < 0 || a >= n || seen[(size_t)a]) bad = true;
+      else seen[(size_t)a] = 1;
+    }
+    if (sweeps_out) sweeps_out[b] = 0;
+    if (bad) {
+      set_status(status, CO_ST_INVALID_TOUR);
+      continue;
+    }
+    const float* lr = locs ? locs + (b % LB) * n * 2 : nullptr;
+    const float* dm = distances ? distances + (b % LB) * n * n : nullptr;
+    auto D = [&](int64_t a, int64_t c) -> float {
+      return dm ? dm[a * n + c] : edge_len(lr[2 * a], lr[2 * a + 1], lr[2 * c], lr[2 * c + 1]);
+    };
+    double min_change = -1.0;
+    int64_t it = 0;
+    while (min_change < -1e-6 && it < max_it) {
+      int64_t p = 0, q = 0;
+      float delta = 0.f;
+      for (int64_t i = 1; i < n - 1; ++i)
+        for (int64_t j = i + 1; j < n; ++j) {
+          const int64_t prev = tour[(size_t)(i - 1)], next = tour[(size_t)((j + 1) % n)];
+          const int64_t ti = tour[(size_t)i], tj = tour[(size_t)j];
+          if (prev == tj || next == ti) continue;
+          const float change = ((D(prev, tj) + D(ti, next)) - D(prev, ti)) - D(tj, next);
+          if (change < delta) {
+            p = i;
+            q = j;
+            delta = change;
+          }
+        }
+      if ((double)delta < -1e-6) {
+        std::reverse(tour.begin() + p, tour.begin() + q + 1);
+        min_change = (double)delta;
+      } else {
+        min_change = 0.0;
+      }
+      ++it;
+    }
+    for (int64_t k = 0; k < n; ++k) out[k] = tour[(size_t)k];
+    if (sweeps_out) sweeps_out[b] = (int32_t)it;
   }
   return CO_OK;
 }

@@ -217,6 +217,29 @@ class TSPEnv(RL4COEnvBase):
         """``tsp/env.py:165-173``."""
         self._get_reward(td, actions, check=True)
 
+    def local_search(self, td, actions, max_iterations: int = 1000, *,
+                     return_sweeps: bool = False):
+        """``tsp/env.py:192-197`` (``tsp/local_search.py:14-74``): best-improvement 2-opt on
+        every row of ``actions`` in one ``co_tsp_two_opt`` launch, on ``td["distances"]``
+        when present, else the Euclidean distances of ``td["locs"]`` (a multistart td's
+        un-replicated ``locs`` read in place, as ``_get_reward`` does).  Returns int64
+        ``[B, N]`` on the actions' device; with ``return_sweeps`` also the sweeps per row.
+        A row that is not a permutation raises ``AssertionError("Invalid tour")`` (the
+        reference does not check)."""
+        from ..utils.ops import two_opt
+
+        raw_get = td.get_raw if hasattr(td, "get_raw") else td.get
+        dist = raw_get("distances", None)
+        raw = dist if dist is not None else raw_get("locs")
+        src = raw.source() if isinstance(raw, RepeatedRows) else raw
+        status = self.status_word(actions.device)
+        res = two_opt(actions, locs=None if dist is not None else src,
+                      distances=src if dist is not None else None,
+                      max_iterations=max_iterations, return_sweeps=return_sweeps,
+                      status=status)
+        self.raise_for_status(status, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])
+        return res
+
     def get_action_mask(self, td):
         return td["action_mask"]
 

@@ -163,6 +163,53 @@ def get_distance_matrix(locs: Tensor) -> Tensor:
     return out.reshape(*lead, n, n)
 
 
+def two_opt(actions: Tensor, locs: Tensor = None, distances: Tensor = None,
+            max_iterations: int = 1000, return_sweeps: bool = False, status: Tensor = None):
+    """``tsp/local_search.py:14-74`` on ``co_tsp_two_opt``: best-improvement 2-opt on every
+    row of ``actions [B, N]`` (any strides, any integer dtype), the whole search in one
+    launch.  Exactly one of ``locs [LB, N, 2]`` and ``distances [LB, N, N]`` (f32) is
+    given; row ``b`` uses instance ``b % LB`` (``LB == B`` normally; the multistart layout
+    passes the un-replicated instances).  Returns int64 ``[B, N]`` on the actions' device,
+    with ``return_sweeps`` also the sweeps executed per row (int32 ``[B]``).  A row that is
+    not a permutation raises ``AssertionError("Invalid tour")`` -- or, with a caller-held
+    ``status`` word, sets ``ST_INVALID_TOUR`` there and the caller reads it."""
+    if (locs is None) == (distances is None):
+        raise ValueError("two_opt: give exactly one of locs and distances")
+    src = locs if locs is not None else distances
+    nat.require_device(actions, src)
+    if actions.dim() != 2:
+        raise ValueError(f"two_opt: actions must be [B, N], got {tuple(actions.shape)}")
+    b, n = actions.shape
+    if n > nat.TWO_OPT_MAX_N:
+        raise ValueError(f"two_opt: num_loc {n} exceeds the supported maximum "
+                         f"{nat.TWO_OPT_MAX_N}")
+    want = (n, 2) if locs is not None else (n, n)
+    if src.dim() != 3 or tuple(src.shape[1:]) != want or src.shape[0] == 0 \
+            or b % src.shape[0] != 0:
+        raise ValueError(f"two_opt: {'locs' if locs is not None else 'distances'} of shape "
+                         f"{tuple(src.shape)} does not fit actions {tuple(actions.shape)}")
+    src = src.contiguous().float()
+    if actions.dtype != torch.int64:
+        actions = actions.long()
+    out = torch.empty((b, n), dtype=torch.int64, device=actions.device)
+    sweeps = torch.empty(b, dtype=torch.int32, device=actions.device) if return_sweeps else None
+    if b == 0 or n == 0:
+        return (out, sweeps) if return_sweeps else out
+    own = status is None
+    if own:
+        status = nat.scratch_status(actions.device)
+    nat.call("co_tsp_two_opt", b, n, nat.ptr(src) if locs is not None else None,
+             nat.ptr(src) if locs is None else None, src.shape[0], nat.ptr(actions),
+             actions.stride(0), actions.stride(1), int(max_iterations), nat.ptr(out),
+             nat.ptr(sweeps), nat.ptr(status), nat.stream_of(actions))
+    if own:
+        bits = int(status.item())
+        nat.release_status(status, (bits,))
+        if bits & nat.ST_INVALID_TOUR:
+            raise AssertionError("Invalid tour")
+    return (out, sweeps) if return_sweeps else out
+
+
 def get_num_starts(td, env_name=None):
     """``ops.py:126-136``."""
     n = td["action_mask"].shape[-1]
