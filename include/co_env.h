@@ -161,6 +161,70 @@ int co_cvrp_reward(int64_t batch, int64_t num_loc, int64_t steps, const float* l
                    const float* demand, const float* vehicle_capacity, int check, float* reward,
                    int32_t* status, void* stream);
 
+/* Post-hoc improvement of CVRP rollouts: best-improvement 2-opt and relocate on the giant
+ * tour of every row, the whole search of a row in one launch.  (The reference's
+ * cvrp/local_search.py hands each instance to PyVRP with a randomised operator set and
+ * growing load penalties; that is not reproduced.  This entry gives the capability: a
+ * shorter, still feasible action matrix, deterministically.)
+ *
+ * Distances.  Exactly one of locs (f32 [LB, N+1, 2], depot first) and distances
+ * (f32 [LB, N+1, N+1], row = first operand) is non-NULL; D[a, c] is distances[a, c] or the
+ * f32 sqrt(dx*dx + dy*dy) co_distance_matrix writes (no FMA).  Row b uses instance b % LB
+ * of locs / distances / demand [LB, N] / capacity [LB] (NULL = 1.0 for every row).
+ *
+ * Row check.  Every entry of the row (element (b, t) at actions[b*act_stride_b +
+ * t*act_stride_t]) lies in 0..N, each of 1..N occurs exactly once, and each demand and the
+ * capacity is finite and in [0, 4096]; otherwise the row is copied unchanged with 0 sweeps
+ * and CO_ST_INVALID_TOUR is set.  A row that breaks capacity on input is not an error.
+ *
+ * Giant tour.  g[0] = 0, then the row's entries in order without a 0 that would follow a
+ * 0, without a trailing 0; m = len(g) = N + the number of non-empty routes.  The tour is
+ * cyclic (position m is position 0), g[0] never moves and m stays fixed: a route may
+ * become empty, leaving two adjacent zeros.
+ *
+ * Loads.  q(x) = llrint((double)x * 2^40) in int64, so route loads are exact integer sums
+ * and do not depend on order; cap_q = q(capacity) + 2^20.  (The generator's k / capacity
+ * demands are rounded f32 values and routes that fill the vehicle exactly are common; the
+ * slack of 9.5e-7 admits them and stays far inside the validity scan's 1e-5.)
+ *
+ * One sweep scores every candidate in f32, left to right as bracketed:
+ *  - 2-opt (i, j), 1 <= i < j <= m-1: reverse g[i..j].  With p = g[i-1], x = g[i],
+ *    y = g[j], n = g[(j+1) % m]:
+ *      change = ((D[p,y] + D[x,n]) - D[p,x]) - D[y,n]
+ *    (no skip test: reversing across a depot merges or re-cuts routes).  Admissible if
+ *    g[i..j] holds no 0; otherwise both new boundary routes must have load <= cap_q:
+ *    left = the customers of i-1's route at positions < i plus those after the last 0 of
+ *    the segment up to j; right = the customers from i up to the first 0 of the segment
+ *    plus those after j to the end of that route.  Routes wholly inside the segment are
+ *    only reversed.
+ *  - relocate (i, j), g[i] != 0, j in 0..m-1, j != i, j != i-1: customer c = g[i] moves
+ *    to between positions j and j+1.  With p = g[i-1], n = g[(i+1) % m], a = g[j],
+ *    b = g[(j+1) % m]:
+ *      change = ((D[a,c] + D[c,b]) - D[a,b]) + ((D[p,n] - D[p,c]) - D[c,n])
+ *    Admissible if gap j lies in c's own route (as many zeros in g[0..j] as in g[0..i]);
+ *    otherwise the target route's load plus q(demand[c]) must be <= cap_q.
+ * The smallest change among the admissible candidates with change < 0 is taken (equal
+ * values: 2-opt before relocate, then the smaller i, then the smaller j) and applied when
+ * it is < -1e-6 (compared in double): one move per sweep.  The search ends with the first
+ * sweep that applies nothing or after max_iterations sweeps (<= 0: no sweep; above
+ * 2^31 - 1 counts as 2^31 - 1).
+ *
+ * Output.  actions_out[batch, steps] (row-major; must not alias actions) receives the
+ * routes of g in order, separated by single zeros, without a leading zero or empty routes,
+ * padded with zeros to width steps -- a valid row with 0 sweeps comes back compacted.
+ * sweeps_out[batch] (nullable) receives the sweeps executed.
+ *
+ * Limits: steps >= num_loc >= 1 and min(steps, 2*num_loc) + 1 <= CO_CVRP_LS_MAX_LEN, else
+ * CO_E_INVAL.  One wavefront per row, tour state in LDS; a distances matrix of
+ * num_loc <= CO_CVRP_LS_STAGE_N is staged in LDS, larger ones are read through L2. */
+#define CO_CVRP_LS_MAX_LEN 1024
+#define CO_CVRP_LS_STAGE_N 117
+int co_cvrp_local_search(int64_t batch, int64_t num_loc, int64_t steps, const float* locs,
+                         const float* distances, const float* demand, const float* capacity,
+                         int64_t locs_batch, const int64_t* actions, int64_t act_stride_b,
+                         int64_t act_stride_t, int64_t max_iterations, int64_t* actions_out,
+                         int32_t* sweeps_out, int32_t* status, void* stream);
+
 /* ----------------------------------------------------------------- SLAP */
 
 /* SLAPEnv._reset (rl4co/envs/warehousing/slap/env.py:95-129). L = n_aisles*n_locs,

@@ -37,6 +37,8 @@ _SIGS = {
     "co_cvrp_step": [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "co_cvrp_action_mask": [_i64, _i64, _p, _p, _p, _p, _p, _p, _p],
     "co_cvrp_reward": [_i64, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _i32, _p, _p, _p],
+    "co_cvrp_local_search": [_i64, _i64, _i64, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p,
+                             _p, _p, _p],
     "co_slap_reset": [_i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
     "co_slap_step": [_i64, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "co_slap_reward": [_i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p],
@@ -90,6 +92,8 @@ DECODE_FAST = 0x100  # CO_DECODE_FAST mode flag (opt-in fast math; not bit-exact
 DECODE_CERTIFIED = 0x200  # CO_DECODE_CERTIFIED: fast math, greedy actions certified exact
 TWO_OPT_MAX_N = 1024  # CO_TWO_OPT_MAX_N: the longest tour co_tsp_two_opt takes
 TWO_OPT_STAGE_N = 126 # CO_TWO_OPT_STAGE_N: distance matrices up to this N are staged in LDS
+CVRP_LS_MAX_LEN = 1024  # CO_CVRP_LS_MAX_LEN: min(steps, 2*num_loc) + 1 may not exceed it
+CVRP_LS_STAGE_N = 117   # CO_CVRP_LS_STAGE_N: distance matrices up to this N are staged in LDS
 
 _lock = threading.Lock()
 _lib = None
@@ -143,6 +147,7 @@ _host = None
 HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt",
                 "co_any_eq_i64",
                 "co_cvrp_reset", "co_cvrp_step", "co_cvrp_action_mask", "co_cvrp_reward",
+                "co_cvrp_local_search",
                 "co_slap_reset", "co_slap_step", "co_slap_reward", "co_gather_by_index",
                 "co_decode_step"]
 

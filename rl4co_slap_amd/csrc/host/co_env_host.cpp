@@ -326,6 +326,30 @@ CO_HOST_API int co_any_eq_i64(const int64_t* x, int64_t n, int64_t value, int32_
 
 // ---------------------------------------------------------------------------- CVRP
 namespace {
+// co_cvrp_local_search's state of one row: the giant tour and, per position k, the load of
+// k's route up to and including k (head), from k to the route's end (tail; tail[m] = 0) and
+// the last zero at or before k (pz).  With these every admissibility test is O(1).
+struct GiantTour {
+  int64_t m = 0;
+  std::vector<int64_t> g, q, head, tail, pz;  // q: quantised demand of node id
+  void rebuild() {
+    head.assign((size_t)m + 1, 0);
+    tail.assign((size_t)m + 1, 0);
+    pz.assign((size_t)m + 1, 0);
+    for (int64_t k = 1; k < m; ++k) {
+      const bool z = g[(size_t)k] == 0;
+      head[(size_t)k] = z ? 0 : head[(size_t)k - 1] + q[(size_t)g[(size_t)k]];
+      pz[(size_t)k] = z ? k : pz[(size_t)k - 1];
+    }
+    for (int64_t k = m - 1; k >= 1; --k)
+      tail[(size_t)k] = g[(size_t)k] == 0 ? 0 : tail[(size_t)k + 1] + q[(size_t)g[(size_t)k]];
+  }
+  int64_t at(int64_t k) const { return g[(size_t)(k >= m ? k - m : k)]; }  // cyclic
+};
+
+inline bool cvrp_ls_scalar_ok(float x) { return std::isfinite(x) && x >= 0.f && x <= 4096.f; }
+inline int64_t cvrp_ls_q(float x) { return std::llrint((double)x * 1099511627776.0); }  // 2^40
+
 // cvrp/env.py:137-149: mask_loc = visited[1:] | (demand + used > capacity);
 // depot feasible unless (current == 0 and some customer is feasible)
 void cvrp_mask_row(int64_t N, const float* dem, float used, float cap, const uint8_t* vis,
@@ -471,6 +495,121 @@ CO_HOST_API int co_cvrp_reward(int64_t B, int64_t N, int64_t T, const float* loc
         break;
       }
     }
+  }
+  return CO_OK;
+}
+
+// Giant-tour 2-opt + relocate (no reference counterpart that can be reproduced: cvrp/
+// local_search.py hands the instance to PyVRP).  The header states the search; this is its
+// plain scalar form: candidates in tie order (2-opt, then relocate; i, then j ascending)
+// against a strict `<` from 0, so equal changes keep the first.
+CO_HOST_API int co_cvrp_local_search(int64_t B, int64_t N, int64_t T, const float* locs,
+                                     const float* distances, const float* demand,
+                                     const float* capacity, int64_t LB, const int64_t* actions,
+                                     int64_t sb, int64_t st, int64_t max_iterations,
+                                     int64_t* actions_out, int32_t* sweeps_out, int32_t* status,
+                                     void*) {
+  if (B < 0 || N < 1 || T < N) return CO_E_INVAL;
+  if ((T < 2 * N ? T : 2 * N) + 1 > CO_CVRP_LS_MAX_LEN) return CO_E_INVAL;
+  if (LB <= 0 || (B > 0 && B % LB != 0)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if ((locs == nullptr) == (distances == nullptr)) return CO_E_INVAL;
+  if (!demand || !actions || !actions_out || actions_out == actions || !status)
+    return CO_E_INVAL;
+  const int64_t V = N + 1;  // nodes, depot first
+  const int64_t max_it = max_iterations > INT32_MAX ? INT32_MAX : max_iterations;
+  GiantTour gt;
+  gt.q.assign((size_t)V, 0);
+  std::vector<uint8_t> seen((size_t)V);
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t* ar = actions + b * sb;
+    int64_t* out = actions_out + b * T;
+    const int64_t inst = b % LB;
+    const float* dr = demand + inst * N;
+    const float cap = capacity ? capacity[inst] : 1.0f;
+    std::fill(seen.begin(), seen.end(), 0);
+    bool bad = !cvrp_ls_scalar_ok(cap);
+    int64_t customers = 0;
+    gt.g.assign(1, 0);
+    for (int64_t k = 0; k < T; ++k) {
+      const int64_t a = ar[k * st];
+      out[k] = a;
+      if (a < 0 || a > N || (a > 0 && seen[(size_t)a])) {
+        bad = true;
+        continue;
+      }
+      seen[(size_t)a] = 1;
+      customers += a > 0;
+      if (a != 0 || gt.g.back() != 0) gt.g.push_back(a);
+    }
+    for (int64_t c = 0; c < N; ++c) {
+      if (!cvrp_ls_scalar_ok(dr[c])) bad = true;
+      else gt.q[(size_t)c + 1] = cvrp_ls_q(dr[c]);
+    }
+    if (sweeps_out) sweeps_out[b] = 0;
+    if (bad || customers != N) {
+      set_status(status, CO_ST_INVALID_TOUR);
+      continue;
+    }
+    if (gt.g.size() > 1 && gt.g.back() == 0) gt.g.pop_back();
+    const int64_t m = gt.m = (int64_t)gt.g.size();
+    const int64_t cap_q = cvrp_ls_q(cap) + (int64_t(1) << 20);
+    const float* lr = locs ? locs + inst * V * 2 : nullptr;
+    const float* dm = distances ? distances + inst * V * V : nullptr;
+    auto D = [&](int64_t a, int64_t c) -> float {
+      return dm ? dm[a * V + c] : edge_len(lr[2 * a], lr[2 * a + 1], lr[2 * c], lr[2 * c + 1]);
+    };
+    std::vector<int64_t>& g = gt.g;
+    int64_t it = 0;
+    while (it < max_it) {
+      ++it;
+      gt.rebuild();
+      float best = 0.f;
+      int kind = -1;
+      int64_t bi = 0, bj = 0;
+      for (int64_t i = 1; i < m - 1; ++i)
+        for (int64_t j = i + 1; j < m; ++j) {
+          const int64_t p = g[(size_t)i - 1], x = g[(size_t)i], y = g[(size_t)j], n = gt.at(j + 1);
+          const float change = ((D(p, y) + D(x, n)) - D(p, x)) - D(y, n);
+          if (!(change < best)) continue;
+          if (gt.pz[(size_t)j] >= i &&  // a depot inside: both new boundary routes must fit
+              (gt.head[(size_t)i - 1] + gt.head[(size_t)j] > cap_q ||
+               gt.tail[(size_t)i] + gt.tail[(size_t)j + 1] > cap_q))
+            continue;
+          best = change;
+          kind = 0;
+          bi = i;
+          bj = j;
+        }
+      for (int64_t i = 1; i < m; ++i) {
+        const int64_t c = g[(size_t)i];
+        if (c == 0) continue;
+        const int64_t p = g[(size_t)i - 1], n = gt.at(i + 1);
+        const float gain = (D(p, n) - D(p, c)) - D(c, n);
+        for (int64_t j = 0; j < m; ++j) {
+          if (j == i || j == i - 1) continue;
+          const int64_t a = g[(size_t)j], e = gt.at(j + 1);
+          const float change = ((D(a, c) + D(c, e)) - D(a, e)) + gain;
+          if (!(change < best)) continue;
+          if (gt.pz[(size_t)j] != gt.pz[(size_t)i] &&  // another route: it must take c
+              gt.head[(size_t)j] + gt.tail[(size_t)j + 1] + gt.q[(size_t)c] > cap_q)
+            continue;
+          best = change;
+          kind = 1;
+          bi = i;
+          bj = j;
+        }
+      }
+      if (kind < 0 || !((double)best < -1e-6)) break;
+      if (kind == 0) std::reverse(g.begin() + bi, g.begin() + bj + 1);
+      else if (bj > bi) std::rotate(g.begin() + bi, g.begin() + bi + 1, g.begin() + bj + 1);
+      else std::rotate(g.begin() + bj + 1, g.begin() + bi, g.begin() + bi + 1);
+    }
+    int64_t w = 0;
+    for (int64_t k = 1; k < m; ++k)
+      if (g[(size_t)k] != 0 || (w > 0 && out[w - 1] != 0)) out[w++] = g[(size_t)k];
+    for (; w < T; ++w) out[w] = 0;
+    if (sweeps_out) sweeps_out[b] = (int32_t)it;
   }
   return CO_OK;
 }

@@ -39,24 +39,6 @@ static_assert(4 * CO_TWO_OPT_STAGE_N * CO_TWO_OPT_STAGE_N + 8 * (CO_TWO_OPT_STAG
               "a staged matrix with the tour and edge terms must fit 64 KiB of LDS");
 static_assert(CO_TWO_OPT_MAX_N < (1 << 15), "move keys pack j <= n into 16 bits");
 
-struct Move {
-  int i, j;
-};
-
-// Element c of strip row q (0 <= c <= n): row q holds diagonal r = q + 1 (n - r elements,
-// the closing one included) and then diagonal n-1-r (r + 1 elements).  An odd middle
-// diagonal (n-1)/2 ends the strip as the first part of a last, half-filled row.
-// j == n marks a closing element.
-__device__ __forceinline__ Move strip_move(int q, int c, int n) {
-  const int r = q + 1, a = n - r;
-  const bool first = c < a;
-  const int d = first ? r : n - 1 - r, t = first ? c : c - a;
-  Move m;
-  m.i = 1 + t;
-  m.j = 1 + t + d;
-  return m;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(64) void two_opt_kernel(
     int64_t B, int n, const float* __restrict__ src, int64_t LB,
@@ -132,7 +114,7 @@ __global__ __launch_bounds__(64) void two_opt_kernel(
       // last element is a closing one, so the last move is at total - 2
       for (int x0 = 0; x0 < total - 1; x0 += kStep) {
         const bool live = x0 + lane < total;
-        const Move m = strip_move(live ? q : 0, live ? c : 0, n);  // idle lanes: move (1, 2)
+        const StripMove m = strip_move(live ? q : 0, live ? c : 0, n);  // idle lanes: move (1, 2)
         const float g = dist(m.i - 1, m.j);
         // D[t[i], t[j+1]] is the successor's g: DPP wave_shl:1, lane l reads lane l + 1
         // (lane 63 reads 0 and owns no move)

@@ -7,7 +7,7 @@ import torch
 from torch.distributions import Uniform
 
 from .. import _native as nat
-from ..td import TensorDict, set_many
+from ..td import RepeatedRows, TensorDict, set_many
 from .base import RL4COEnvBase
 from .common import Generator, device_uniform, get_sampler
 
@@ -265,6 +265,45 @@ class CVRPEnv(RL4COEnvBase):
     def check_solution_validity(self, td, actions):
         """``cvrp/env.py:162-190``."""
         self._get_reward(td, actions, check=True)
+
+    # keywords of the reference's cvrp/local_search.py (its PyVRP run): accepted, no effect
+    _REFERENCE_LS_KWARGS = frozenset({"max_trials", "neighbourhood_params", "load_penalty",
+                                      "allow_infeasible_solution", "seed", "num_workers"})
+
+    def improve(self, td, actions, max_iterations: int = 1000, *, return_sweeps: bool = False,
+                **reference_kwargs):
+        """Post-hoc improvement of rollouts (the role of ``cvrp/local_search.py``, whose
+        PyVRP run is not reproduced): best-improvement 2-opt + relocate on the giant tour of
+        every row of ``actions [B, T]`` in one ``co_cvrp_local_search`` launch, on
+        ``td["distances"]`` when present, else the Euclidean distances of the post-reset
+        ``td["locs"]`` (depot first), with ``td["demand"]`` and ``td["vehicle_capacity"]``.
+        A multistart td's un-replicated entries (``RepeatedRows``) are read in place.
+        Returns int64 ``[B, T]`` on the actions' device -- shorter or equal, still feasible
+        when the input was -- with ``return_sweeps`` also the sweeps per row.  A row that
+        does not visit every customer exactly once raises ``AssertionError("Invalid
+        tour")``.  The reference-only keywords are accepted and ignored."""
+        from ..utils.ops import cvrp_local_search
+
+        unknown = set(reference_kwargs) - self._REFERENCE_LS_KWARGS
+        if unknown:
+            raise TypeError(f"improve() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+        raw_get = td.get_raw if hasattr(td, "get_raw") else td.get
+        dist = raw_get("distances", None)
+        raws = [dist if dist is not None else raw_get("locs"), raw_get("demand"),
+                raw_get("vehicle_capacity")]
+        if all(isinstance(r, RepeatedRows) for r in raws) \
+                and len({r.repeats for r in raws}) == 1:
+            src, demand, vcap = (r.source() for r in raws)
+        else:
+            src, demand, vcap = (r.materialize() if isinstance(r, RepeatedRows) else r
+                                 for r in raws)
+        status = self.status_word(actions.device)
+        res = cvrp_local_search(actions, demand, locs=None if dist is not None else src,
+                                distances=src if dist is not None else None, capacity=vcap,
+                                max_iterations=max_iterations, return_sweeps=return_sweeps,
+                                status=status)
+        self.raise_for_status(status, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])
+        return res
 
     @staticmethod
     def load_data(fpath, batch_size=[]):

@@ -210,6 +210,67 @@ def two_opt(actions: Tensor, locs: Tensor = None, distances: Tensor = None,
     return (out, sweeps) if return_sweeps else out
 
 
+def cvrp_local_search(actions: Tensor, demand: Tensor, locs: Tensor = None,
+                      distances: Tensor = None, capacity: Tensor = None,
+                      max_iterations: int = 1000, return_sweeps: bool = False,
+                      status: Tensor = None):
+    """Best-improvement 2-opt + relocate on the giant tour of every row of ``actions
+    [B, T]`` (any strides, any integer dtype) on ``co_cvrp_local_search``, the whole search
+    in one launch (``include/co_env.h`` states the moves, the integer capacity test and the
+    tie rule).  ``demand [LB, N]`` and exactly one of ``locs [LB, N+1, 2]`` (depot first)
+    and ``distances [LB, N+1, N+1]`` (f32) are given, ``capacity [LB]`` or ``[LB, 1]``
+    optionally (default 1.0); row ``b`` uses instance ``b % LB``.  Returns int64 ``[B, T]``
+    on the actions' device -- the routes separated by single zeros and padded with zeros --
+    with ``return_sweeps`` also the sweeps executed per row (int32 ``[B]``).  A row that
+    does not visit every customer exactly once (or whose demands / capacity are not finite
+    values in [0, 4096]) raises ``AssertionError("Invalid tour")`` -- or, with a caller-held
+    ``status`` word, sets ``ST_INVALID_TOUR`` there and comes back unchanged."""
+    if (locs is None) == (distances is None):
+        raise ValueError("cvrp_local_search: give exactly one of locs and distances")
+    src = locs if locs is not None else distances
+    nat.require_device(actions, demand, src, capacity)
+    if actions.dim() != 2 or demand.dim() != 2:
+        raise ValueError(f"cvrp_local_search: actions must be [B, T] and demand [LB, N], got "
+                         f"{tuple(actions.shape)} and {tuple(demand.shape)}")
+    b, t = actions.shape
+    lb, n = demand.shape
+    if n < 1 or t < n:
+        raise ValueError(f"cvrp_local_search: {t} steps cannot visit {n} customers")
+    if min(t, 2 * n) + 1 > nat.CVRP_LS_MAX_LEN:
+        raise ValueError(f"cvrp_local_search: a giant tour of up to {min(t, 2 * n) + 1} "
+                         f"positions exceeds the supported maximum {nat.CVRP_LS_MAX_LEN}")
+    want = (lb, n + 1, 2) if locs is not None else (lb, n + 1, n + 1)
+    if tuple(src.shape) != want or lb == 0 or b % lb != 0:
+        raise ValueError(f"cvrp_local_search: {'locs' if locs is not None else 'distances'} of "
+                         f"shape {tuple(src.shape)} does not fit actions {tuple(actions.shape)} "
+                         f"and demand {tuple(demand.shape)}")
+    if capacity is not None:
+        if capacity.numel() != lb:
+            raise ValueError(f"cvrp_local_search: capacity of shape {tuple(capacity.shape)} "
+                             f"does not fit demand {tuple(demand.shape)}")
+        capacity = capacity.reshape(lb).contiguous().float()
+    src, demand = src.contiguous().float(), demand.contiguous().float()
+    if actions.dtype != torch.int64:
+        actions = actions.long()
+    out = torch.empty((b, t), dtype=torch.int64, device=actions.device)
+    sweeps = torch.empty(b, dtype=torch.int32, device=actions.device) if return_sweeps else None
+    if b == 0:
+        return (out, sweeps) if return_sweeps else out
+    own = status is None
+    if own:
+        status = nat.scratch_status(actions.device)
+    nat.call("co_cvrp_local_search", b, n, t, nat.ptr(src) if locs is not None else None,
+             nat.ptr(src) if locs is None else None, nat.ptr(demand), nat.ptr(capacity), lb,
+             nat.ptr(actions), actions.stride(0), actions.stride(1), int(max_iterations),
+             nat.ptr(out), nat.ptr(sweeps), nat.ptr(status), nat.stream_of(actions))
+    if own:
+        bits = int(status.item())
+        nat.release_status(status, (bits,))
+        if bits & nat.ST_INVALID_TOUR:
+            raise AssertionError("Invalid tour")
+    return (out, sweeps) if return_sweeps else out
+
+
 def get_num_starts(td, env_name=None):
     """``ops.py:126-136``."""
     n = td["action_mask"].shape[-1]

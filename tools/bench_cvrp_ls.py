@@ -1,0 +1,132 @@
+"""co_cvrp_local_search (CVRPEnv.improve) on uniform CVRP-100 at B = 8,192 and CVRP-20 at
+B = 65,536, from random split tours (a random permutation cut where the load would pass the
+capacity) and from nearest-feasible greedy tours (measurement tool, not part of the
+product).  Per case: ms per ``ops.cvrp_local_search`` call (median of 5 calls after a
+warm-up, by device events around the call), the total sweeps (sweeps_out) and candidate
+evaluations per second, counted as sum over rows of sweeps * ((m-1)(m-2)/2 + N(m-2)) with
+m = N + the row's routes.  The host build is timed in the same run on the first 256 rows
+(wall clock, one thread: the host library is single-threaded) and its results are compared
+with the device's.
+Usage: python tools/bench_cvrp_ls.py [--quick] -> one JSON line."""
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from rl4co_slap_amd import _native as nat  # noqa: E402
+from rl4co_slap_amd.envs.cvrp import CAPACITIES  # noqa: E402
+from rl4co_slap_amd.utils.ops import cvrp_local_search, get_distance_matrix  # noqa: E402
+
+HOST_ROWS, HOST_THREADS = 256, 1
+
+
+def split_tours(demand, gen):
+    """Random permutations of the customers, cut where the f32 running load would pass 1."""
+    b, n = demand.shape
+    dev = demand.device
+    perm = torch.rand(b, n, generator=gen).argsort(1).to(dev)
+    rows = torch.arange(b, device=dev)
+    out = torch.zeros(b, 2 * n + 1, dtype=torch.int64, device=dev)
+    ptr = torch.zeros(b, dtype=torch.int64, device=dev)
+    used = torch.zeros(b, device=dev)
+    for t in range(n):
+        c = perm[:, t]
+        d = demand[rows, c]
+        over = used + d > 1.0
+        ptr = ptr + over  # a zero stays where the load would pass the capacity
+        used = torch.where(over, torch.zeros_like(used), used)
+        out[rows, ptr] = c + 1
+        ptr = ptr + 1
+        used = used + d
+    return out[:, : int(ptr.max().item()) + 1]
+
+
+def greedy_tours(locs, demand):
+    """From the current node to the nearest unvisited customer that still fits (lowest
+    index on ties), to the depot when none fits."""
+    b, n = demand.shape
+    dev = demand.device
+    dist = get_distance_matrix(locs)[:, :, 1:]  # [B, N+1, N]: from any node to a customer
+    rows = torch.arange(b, device=dev)
+    visited = torch.zeros(b, n, dtype=torch.bool, device=dev)
+    cur = torch.zeros(b, dtype=torch.int64, device=dev)
+    used = torch.zeros(b, device=dev)
+    steps = []
+    while not bool(visited.all()):
+        blocked = visited | (used[:, None] + demand > 1.0)
+        home = blocked.all(1)
+        nxt = dist[rows, cur].masked_fill(blocked, float("inf")).argmin(1)
+        act = torch.where(home, torch.zeros_like(nxt), nxt + 1)
+        go = ~home
+        visited[rows[go], nxt[go]] = True
+        used = torch.where(home, torch.zeros_like(used), used + demand[rows, nxt])
+        cur = act
+        steps.append(act)
+    return torch.stack(steps + [torch.zeros_like(cur)], 1)
+
+
+def evaluations(tours, sweeps, n):
+    prev = torch.cat([torch.zeros_like(tours[:, :1]), tours[:, :-1]], 1)
+    m = n + ((tours != 0) & (prev == 0)).sum(1)
+    per_sweep = (m - 1) * (m - 2) // 2 + n * (m - 2)
+    return int((per_sweep * sweeps.long()).sum().item()), float(m.float().mean().item())
+
+
+def measure(locs, demand, tours, dev):
+    n = demand.shape[1]
+    out, sweeps = cvrp_local_search(tours, demand, locs=locs, return_sweeps=True)  # warm-up
+    torch.cuda.synchronize(dev)
+    ms = []
+    for _ in range(5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out, sweeps = cvrp_local_search(tours, demand, locs=locs, return_sweeps=True)
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    ms = statistics.median(ms)
+    total = int(sweeps.sum().item())
+    evals, m_mean = evaluations(tours, sweeps, n)
+    hl, hd, ht = locs[:HOST_ROWS].cpu(), demand[:HOST_ROWS].cpu(), tours[:HOST_ROWS].cpu()
+    t0 = time.perf_counter()
+    hout, hsw = cvrp_local_search(ht, hd, locs=hl, return_sweeps=True)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    host_evals, _ = evaluations(ht, hsw, n)
+    same = bool(torch.equal(hout, out[:HOST_ROWS].cpu())
+                and torch.equal(hsw, sweeps[:HOST_ROWS].cpu()))
+    return {"ms_per_call_events": round(ms, 4), "steps": tours.shape[1],
+            "tour_positions_mean": round(m_mean, 1), "sweeps_total": total,
+            "sweeps_mean": round(total / tours.shape[0], 2),
+            "sweeps_max": int(sweeps.max().item()),
+            "candidate_evals_per_s": round(evals / (ms * 1e-3), 1),
+            "host_rows": hl.shape[0], "host_threads": HOST_THREADS,
+            "host_ms_wall": round(host_ms, 2),
+            "host_candidate_evals_per_s": round(host_evals / (host_ms * 1e-3), 1),
+            "host_equals_device": same}
+
+
+def main():
+    quick = "--quick" in sys.argv
+    dev = torch.device("cuda:0")
+    nat.load()
+    nat.load_host()
+    res = {"device": torch.cuda.get_device_name(0)}
+    for n, b in ((100, 8192), (20, 65536)):
+        if quick:
+            b //= 16
+        g = torch.Generator().manual_seed(n)
+        locs = torch.rand(b, n + 1, 2, generator=g).to(dev)
+        demand = (torch.randint(1, 10, (b, n), generator=g).float() / CAPACITIES[n]).to(dev)
+        res[f"cvrp{n}_b{b}_split"] = measure(locs, demand, split_tours(demand, g), dev)
+        res[f"cvrp{n}_b{b}_greedy"] = measure(locs, demand, greedy_tours(locs, demand), dev)
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
