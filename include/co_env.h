@@ -257,6 +257,87 @@ int co_slap_reward(int64_t batch, int64_t num_slots, int64_t n_products, int64_t
                    int64_t order_size, const int32_t* assignment, const int64_t* picklist,
                    const float* locs, float* reward, int32_t* status, void* stream);
 
+/* Post-hoc improvement of SLAP assignments: best-improvement product swap + relocate, the
+ * whole search of a row in one launch.  (The reference has no local search for SLAP;
+ * SLAPEnv.local_search raises there.  The objective of slap/env.py:131-143 is a quadratic
+ * assignment objective -- flow = how often product a is followed by product c in a
+ * picklist, distance = slot to slot -- and this entry runs the classical QAP
+ * neighbourhood on it, deterministically.)
+ *
+ * Inputs.  Exactly one of locs (f32 [LB, L, 2]) and distances (f32 [LB, L, L], row = first
+ * operand, may be asymmetric) is non-NULL; D[u, v] is distances[u, v] or the f32
+ * sqrt(dx*dx + dy*dy) co_distance_matrix writes (no FMA).  picklist is int64 [LB, O, K],
+ * assignment int32 [B, P]: s[p] is the slot of product p.  Row b uses instance b % LB of
+ * locs / distances / picklist (the un-replicated multistart layout).
+ *
+ * Objective, exact in integers.  Q[u][v] = llrint((double)D[u][v] * 2^20) in int64.
+ * W[a][c] = the number of pairs (o, k) with picklist[o, k] = a, picklist[o, (k+1) % K] = c
+ * and a != c (equal neighbours contribute nothing; W[a][c] <= O * (K / 2)).
+ *   F(s) = sum over a, c of W[a][c] * Q[s[a]][s[c]]
+ * With locs, F / 2^20 is -reward of co_slap_reward up to rounding.  Every sum is an exact
+ * int64 (Q <= 2^40, a row of W sums to <= 2^16), so a candidate's change F(s') - F(s) does
+ * not depend on how or in which order it is evaluated: the device's two evaluation
+ * schemes, the host build and tests/slap_ls_ref.py are bit-equal.
+ *
+ * One sweep.  The candidates are
+ *  - move (p, x): product p goes to slot x, 1 <= x <= L-1, x free (no product sits there).
+ *    Slot 0 is the depot, which the env never offers (slap/env.py:116), so it is never a
+ *    target; a product that already sits at slot 0 may leave it or be swapped.
+ *  - swap (p, q), p < q: the two products exchange slots.
+ * The candidate with the smallest change among those with change < 0 is applied, one per
+ * sweep; equal changes: move before swap, then the smaller p, then the smaller x or q.
+ * The search ends with the first sweep that applies nothing or after max_iterations sweeps
+ * (<= 0: no sweep; above 2^31 - 1 counts as 2^31 - 1).  F strictly decreases, so it ends.
+ *
+ * Outputs.  assign_out [B, P] (must not alias assignment) receives the row;
+ * sweeps_out [B] (nullable) the sweeps executed, the last one that applied nothing
+ * included; cost_out [B] (nullable) F of the returned row.
+ *
+ * Row check.  Every s[p] lies in 0..L-1 and the slots are pairwise distinct (-1, the
+ * unassigned product, is invalid); every picklist entry of the instance lies in 0..P-1
+ * (no wrapping of negative entries); every coordinate of the instance is finite with
+ * |coord| <= 2^18, or every entry of the instance's matrix is finite and in [0, 2^20].
+ * A failing row is copied unchanged with 0 sweeps and cost_out = -1; it sets
+ * CO_ST_INVALID_TOUR for an assignment or distance failure and CO_ST_INDEX_RANGE for a
+ * picklist failure.
+ *
+ * Limits: 1 <= P <= CO_SLAP_LS_MAX_PRODUCTS, P <= L <= CO_SLAP_LS_MAX_SLOTS and
+ * 1 <= O*K <= 65536, else CO_E_INVAL.
+ *
+ * Device.  One wavefront per row; W, s, the occupancy bitmap and the coordinates in LDS.
+ * Two evaluation schemes with identical output: when it fits the LDS budget
+ * (CO_SLAP_LS_TABLE_FITS(P, L): e.g. L <= 383 at P = 20, L <= 239 at P = 32, P = L <= 80)
+ * the QAP table C[p][l] = sum over q of W[p][q]*Q[l][s[q]] + W[q][p]*Q[s[q]][l] is held in
+ * LDS (a move costs C[p][x] - C[p][s[p]]; a swap two such differences and a
+ * W[p][q] + W[q][p] term; an applied move updates O(P*L) entries); otherwise every
+ * candidate is evaluated directly in O(P) terms.  A distances matrix is read through L2 by
+ * both schemes (staging it in LDS was measured slower: DESIGN.md).
+ * co_slap_local_search_scheme is the same entry with the scheme forced (CO_SLAP_LS_AUTO /
+ * _DIRECT / _TABLE; _TABLE where the table does not fit is CO_E_INVAL): for tests and
+ * measurements of one scheme against the other; device library only. */
+#define CO_SLAP_LS_MAX_PRODUCTS 128
+#define CO_SLAP_LS_MAX_SLOTS 1024
+#define CO_SLAP_LS_LDS_BYTES 65536
+/* an upper bound of the LDS bytes of a row's state without the table, and the table's cut */
+#define CO_SLAP_LS_STATE_BYTES(P, L) (2 * (P) * ((P) + 1) + 4 * (P) + 8 * (L) + (L) / 8 + 64)
+#define CO_SLAP_LS_TABLE_FITS(P, L) \
+  (8 * (P) * (L) + CO_SLAP_LS_STATE_BYTES(P, L) <= CO_SLAP_LS_LDS_BYTES)
+#define CO_SLAP_LS_AUTO 0
+#define CO_SLAP_LS_DIRECT 1
+#define CO_SLAP_LS_TABLE 2
+int co_slap_local_search(int64_t batch, int64_t num_slots, int64_t n_products,
+                         int64_t n_orders, int64_t order_size, const float* locs,
+                         const float* distances, int64_t locs_batch, const int64_t* picklist,
+                         const int32_t* assignment, int64_t max_iterations, int32_t* assign_out,
+                         int32_t* sweeps_out, int64_t* cost_out, int32_t* status, void* stream);
+int co_slap_local_search_scheme(int64_t batch, int64_t num_slots, int64_t n_products,
+                                int64_t n_orders, int64_t order_size, const float* locs,
+                                const float* distances, int64_t locs_batch,
+                                const int64_t* picklist, const int32_t* assignment,
+                                int64_t max_iterations, int32_t* assign_out,
+                                int32_t* sweeps_out, int64_t* cost_out, int32_t scheme,
+                                int32_t* status, void* stream);
+
 /* ------------------------------------------------------------ utilities */
 
 /* utils.ops.gather_by_index (rl4co/utils/ops.py:65-77), gather along one dim:

@@ -42,6 +42,10 @@ _SIGS = {
     "co_slap_reset": [_i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
     "co_slap_step": [_i64, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "co_slap_reward": [_i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p],
+    "co_slap_local_search": [_i64, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _p, _p, _p,
+                             _p, _p],
+    "co_slap_local_search_scheme": [_i64, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _p,
+                                    _p, _p, _i32, _p, _p],
     "co_gather_by_index": [_p, _i64, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p],
     "co_any_eq_i64": [_p, _i64, _i64, _p, _p],
     "co_decode_step": [_i64, _i64, _p, _i64, _p, _f32, _f32, _i32, _p, _p, _p, _p, _u64, _u64,
@@ -94,6 +98,18 @@ TWO_OPT_MAX_N = 1024  # CO_TWO_OPT_MAX_N: the longest tour co_tsp_two_opt takes
 TWO_OPT_STAGE_N = 126 # CO_TWO_OPT_STAGE_N: distance matrices up to this N are staged in LDS
 CVRP_LS_MAX_LEN = 1024  # CO_CVRP_LS_MAX_LEN: min(steps, 2*num_loc) + 1 may not exceed it
 CVRP_LS_STAGE_N = 117   # CO_CVRP_LS_STAGE_N: distance matrices up to this N are staged in LDS
+SLAP_LS_MAX_PRODUCTS = 128  # CO_SLAP_LS_MAX_PRODUCTS: the most products co_slap_local_search takes
+SLAP_LS_MAX_SLOTS = 1024    # CO_SLAP_LS_MAX_SLOTS: the most slots
+SLAP_LS_LDS_BYTES = 65536   # CO_SLAP_LS_LDS_BYTES: the LDS budget of a row's state
+SLAP_LS_AUTO, SLAP_LS_DIRECT, SLAP_LS_TABLE = 0, 1, 2  # co_slap_local_search_scheme's schemes
+
+
+def slap_ls_table_fits(p: int, l: int) -> bool:
+    """CO_SLAP_LS_TABLE_FITS(P, L): whether co_slap_local_search's device build runs the
+    table scheme (the QAP table beside the row's other state within the LDS budget)."""
+    state = 2 * p * (p + 1) + 4 * p + 8 * l + l // 8 + 64  # CO_SLAP_LS_STATE_BYTES
+    return 8 * p * l + state <= SLAP_LS_LDS_BYTES
+
 
 _lock = threading.Lock()
 _lib = None
@@ -148,7 +164,8 @@ HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt"
                 "co_any_eq_i64",
                 "co_cvrp_reset", "co_cvrp_step", "co_cvrp_action_mask", "co_cvrp_reward",
                 "co_cvrp_local_search",
-                "co_slap_reset", "co_slap_step", "co_slap_reward", "co_gather_by_index",
+                "co_slap_reset", "co_slap_step", "co_slap_reward", "co_slap_local_search",
+                "co_gather_by_index",
                 "co_decode_step"]
 
 

@@ -710,6 +710,132 @@ CO_HOST_API int co_slap_reward(int64_t B, int64_t L, int64_t P, int64_t O, int64
   return CO_OK;
 }
 
+// Product swap + move-to-free-slot on the integer QAP objective (the reference has no SLAP
+// local search).  The header states the search; this is its scalar form on the table
+// C[p][l] = sum_r W[p][r] Q[l][s_r] + W[r][p] Q[s_r][l], updated after each applied move:
+// candidates in tie order (moves, then swaps; p, then x or q ascending) against a strict
+// `<` from 0, so equal changes keep the first.
+CO_HOST_API int co_slap_local_search(int64_t B, int64_t L, int64_t P, int64_t O, int64_t K,
+                                     const float* locs, const float* distances, int64_t LB,
+                                     const int64_t* picklist, const int32_t* assignment,
+                                     int64_t max_iterations, int32_t* assign_out,
+                                     int32_t* sweeps_out, int64_t* cost_out, int32_t* status,
+                                     void*) {
+  if (B < 0 || P < 1 || P > CO_SLAP_LS_MAX_PRODUCTS || L < P || L > CO_SLAP_LS_MAX_SLOTS)
+    return CO_E_INVAL;
+  if (O < 1 || K < 1 || O > 65536 || K > 65536 || O * K > 65536) return CO_E_INVAL;
+  if (LB <= 0 || (B > 0 && B % LB != 0)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if ((locs == nullptr) == (distances == nullptr)) return CO_E_INVAL;
+  if (!picklist || !assignment || !assign_out || assign_out == assignment || !status)
+    return CO_E_INVAL;
+  const int64_t max_it = max_iterations > INT32_MAX ? INT32_MAX : max_iterations;
+  std::vector<int64_t> W((size_t)(P * P)), C((size_t)(P * L)), s((size_t)P), dcol((size_t)L),
+      drow((size_t)L);
+  std::vector<uint8_t> occ((size_t)L);
+  for (int64_t b = 0; b < B; ++b) {
+    const int32_t* ar = assignment + b * P;
+    int32_t* out = assign_out + b * P;
+    const int64_t inst = b % LB;
+    const int64_t* pl = picklist + inst * O * K;
+    const float* lr = locs ? locs + inst * L * 2 : nullptr;
+    const float* dm = distances ? distances + inst * L * L : nullptr;
+    bool bad = false, bad_pl = false;
+    std::fill(occ.begin(), occ.end(), 0);
+    for (int64_t p = 0; p < P; ++p) {
+      const int64_t v = out[p] = ar[p];
+      if (v < 0 || v >= L || occ[(size_t)v]) {
+        bad = true;
+        continue;
+      }
+      occ[(size_t)v] = 1;
+      s[(size_t)p] = v;
+    }
+    std::fill(W.begin(), W.end(), 0);
+    for (int64_t o = 0; o < O; ++o)
+      for (int64_t k = 0; k < K; ++k) {
+        const int64_t a = pl[o * K + k], c = pl[o * K + (k + 1) % K];
+        if (a < 0 || a >= P) bad_pl = true;
+        else if (c >= 0 && c < P && a != c) ++W[(size_t)(a * P + c)];
+      }
+    if (lr) {
+      for (int64_t k = 0; k < 2 * L; ++k) bad |= !(std::fabs(lr[k]) <= 262144.f);
+    } else {
+      for (int64_t k = 0; k < L * L; ++k) bad |= !(dm[k] >= 0.f && dm[k] <= 1048576.f);
+    }
+    if (sweeps_out) sweeps_out[b] = 0;
+    if (cost_out) cost_out[b] = -1;
+    if (bad || bad_pl) {
+      set_status(status, (bad ? CO_ST_INVALID_TOUR : 0) | (bad_pl ? CO_ST_INDEX_RANGE : 0));
+      continue;
+    }
+    auto Q = [&](int64_t u, int64_t v) -> int64_t {
+      const float d = dm ? dm[u * L + v]
+                         : edge_len(lr[2 * u], lr[2 * u + 1], lr[2 * v], lr[2 * v + 1]);
+      return (int64_t)std::llrint((double)d * 1048576.0);  // 2^20
+    };
+    for (int64_t p = 0; p < P; ++p)
+      for (int64_t l = 0; l < L; ++l) {
+        int64_t acc = 0;
+        for (int64_t r = 0; r < P; ++r) {
+          const int64_t w1 = W[(size_t)(p * P + r)], w2 = W[(size_t)(r * P + p)];
+          if (w1) acc += w1 * Q(l, s[(size_t)r]);
+          if (w2) acc += w2 * Q(s[(size_t)r], l);
+        }
+        C[(size_t)(p * L + l)] = acc;
+      }
+    int64_t it = 0;
+    while (it < max_it) {
+      ++it;
+      int64_t best = 0, bp = 0, bx = 0;
+      int kind = -1;
+      for (int64_t p = 0; p < P; ++p) {
+        const int64_t ca = C[(size_t)(p * L + s[(size_t)p])];
+        for (int64_t x = 1; x < L; ++x) {
+          if (occ[(size_t)x]) continue;
+          const int64_t d = C[(size_t)(p * L + x)] - ca;
+          if (d < best) best = d, kind = 0, bp = p, bx = x;
+        }
+      }
+      for (int64_t p = 0; p < P; ++p)
+        for (int64_t q = p + 1; q < P; ++q) {
+          const int64_t a = s[(size_t)p], c = s[(size_t)q];
+          int64_t d = (C[(size_t)(p * L + c)] - C[(size_t)(p * L + a)]) +
+                      (C[(size_t)(q * L + a)] - C[(size_t)(q * L + c)]);
+          const int64_t w = W[(size_t)(p * P + q)] + W[(size_t)(q * P + p)];
+          if (w) d += w * (((Q(a, c) + Q(c, a)) - Q(a, a)) - Q(c, c));
+          if (d < best) best = d, kind = 1, bp = p, bx = q;
+        }
+      if (kind < 0) break;
+      const int64_t a = s[(size_t)bp], x = kind ? s[(size_t)bx] : bx;
+      for (int64_t l = 0; l < L; ++l) {
+        dcol[(size_t)l] = Q(l, x) - Q(l, a);
+        drow[(size_t)l] = Q(x, l) - Q(a, l);
+      }
+      for (int64_t r = 0; r < P; ++r) {
+        int64_t c1 = W[(size_t)(r * P + bp)], c2 = W[(size_t)(bp * P + r)];
+        if (kind) c1 -= W[(size_t)(r * P + bx)], c2 -= W[(size_t)(bx * P + r)];
+        if (c1 == 0 && c2 == 0) continue;
+        for (int64_t l = 0; l < L; ++l)
+          C[(size_t)(r * L + l)] += c1 * dcol[(size_t)l] + c2 * drow[(size_t)l];
+      }
+      s[(size_t)bp] = x;
+      if (kind) s[(size_t)bx] = a;
+      else occ[(size_t)a] = 0, occ[(size_t)x] = 1;
+    }
+    for (int64_t p = 0; p < P; ++p) out[p] = (int32_t)s[(size_t)p];
+    if (sweeps_out) sweeps_out[b] = (int32_t)it;
+    if (cost_out) {
+      int64_t f = 0;
+      for (int64_t a = 0; a < P; ++a)
+        for (int64_t c = 0; c < P; ++c)
+          if (W[(size_t)(a * P + c)]) f += W[(size_t)(a * P + c)] * Q(s[(size_t)a], s[(size_t)c]);
+      cost_out[b] = f;
+    }
+  }
+  return CO_OK;
+}
+
 // ---------------------------------------------------------------------------- ops
 // utils/ops.py:65-77
 CO_HOST_API int co_gather_by_index(const void* src, int64_t outer, int64_t src_len,

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .. import _native as nat
-from ..td import TensorDict, set_many
+from ..td import RepeatedRows, TensorDict, set_many
 from .base import RL4COEnvBase
 from .common import Generator, device_uniform
 
@@ -273,6 +273,45 @@ class SLAPEnv(RL4COEnvBase):
         self.raise_for_status(status, [(nat.ST_INDEX_RANGE, IndexError,
                                         "index out of range in SLAP reward gather")])
         return reward
+
+    def improve(self, td, actions=None, max_iterations: int = 1000, *, metric: str = "euclidean",
+                return_sweeps: bool = False):
+        """Post-hoc improvement of assignments (the reference has no SLAP local search):
+        best-improvement product swap + move-to-free-slot on every row in one
+        ``co_slap_local_search`` launch.  ``actions=None`` reads ``td["assignment"]``; a given
+        ``actions [B, P]`` is a rollout's action matrix in the env's ``arange`` product order
+        (``slap/env.py:107``): column i is product i's slot.  ``metric="euclidean"`` searches
+        on ``td["locs"]`` -- the env's own reward -- and ``metric="dist_mat"`` on
+        ``td["dist_mat"]``; ``td["picklist"]`` gives the flows.  A multistart td's
+        un-replicated entries (``RepeatedRows``) are read in place.  Returns the improved
+        ``[B, P]`` matrix in the input's dtype on its device, with ``return_sweeps`` also the
+        sweeps per row; ``td.set("assignment", env.improve(td))`` followed by
+        ``env.get_reward(td, None)`` gives the improved reward.  A slot outside ``0..L-1``
+        (an unassigned product's -1 included) or taken twice raises
+        ``AssertionError("Invalid assignment")``, a picklist entry outside ``0..P-1``
+        ``IndexError``."""
+        from ..utils.ops import slap_local_search
+
+        if metric not in ("euclidean", "dist_mat"):
+            raise ValueError(f"improve: metric must be 'euclidean' or 'dist_mat', got {metric!r}")
+        raw_get = td.get_raw if hasattr(td, "get_raw") else td.get
+        key = "locs" if metric == "euclidean" else "dist_mat"
+        raws = [raw_get(key), raw_get("picklist")]
+        if all(isinstance(r, RepeatedRows) for r in raws) \
+                and len({r.repeats for r in raws}) == 1:
+            src, picklist = (r.source() for r in raws)
+        else:
+            src, picklist = (r.materialize() if isinstance(r, RepeatedRows) else r for r in raws)
+        assign = td["assignment"] if actions is None else actions
+        status = self.status_word(assign.device)
+        res = slap_local_search(assign, picklist, locs=src if metric == "euclidean" else None,
+                                distances=None if metric == "euclidean" else src,
+                                max_iterations=max_iterations, return_sweeps=return_sweeps,
+                                status=status)
+        self.raise_for_status(status, [
+            (nat.ST_INVALID_TOUR, AssertionError, "Invalid assignment"),
+            (nat.ST_INDEX_RANGE, IndexError, "index out of range in SLAP picklist")])
+        return res
 
     def get_action_mask(self, td):
         return td["action_mask"]

@@ -271,6 +271,101 @@ def cvrp_local_search(actions: Tensor, demand: Tensor, locs: Tensor = None,
     return (out, sweeps) if return_sweeps else out
 
 
+def slap_local_search(assignment: Tensor, picklist: Tensor, locs: Tensor = None,
+                      distances: Tensor = None, max_iterations: int = 1000,
+                      return_sweeps: bool = False, return_cost: bool = False,
+                      status: Tensor = None, scheme: int = nat.SLAP_LS_AUTO):
+    """Best-improvement product swap + move-to-free-slot on every row of ``assignment
+    [B, P]`` (any strides, any integer dtype; column p is product p's slot) on
+    ``co_slap_local_search``, the whole search in one launch (``include/co_env.h`` states
+    the integer objective, the moves and the tie rule).  ``picklist [LB, O, K]`` and exactly
+    one of ``locs [LB, L, 2]`` and ``distances [LB, L, L]`` (f32) are given; row ``b`` uses
+    instance ``b % LB``.  Returns ``[B, P]`` in the input's dtype on its device, with
+    ``return_sweeps`` also the sweeps executed per row (int32 ``[B]``) and with
+    ``return_cost`` the integer objective of the returned row (int64 ``[B]``, distances in
+    units of 2^-20; -1 for a row that failed its check).  A row with a slot outside
+    ``0..L-1`` or taken twice (or a non-finite / out-of-range coordinate or distance)
+    raises ``AssertionError("Invalid assignment")``, a picklist entry outside ``0..P-1``
+    ``IndexError`` -- or, with a caller-held ``status`` word, sets ``ST_INVALID_TOUR`` /
+    ``ST_INDEX_RANGE`` there and comes back unchanged.  ``scheme`` (device only) forces the
+    direct or the table evaluation scheme; the results do not depend on it."""
+    if (locs is None) == (distances is None):
+        raise ValueError("slap_local_search: give exactly one of locs and distances")
+    src = locs if locs is not None else distances
+    nat.require_device(assignment, picklist, src)
+    if assignment.dim() != 2 or picklist.dim() != 3:
+        raise ValueError(f"slap_local_search: assignment must be [B, P] and picklist "
+                         f"[LB, O, K], got {tuple(assignment.shape)} and "
+                         f"{tuple(picklist.shape)}")
+    if assignment.dtype.is_floating_point or assignment.dtype == torch.bool:
+        raise ValueError(f"slap_local_search: assignment must hold integers, got "
+                         f"{assignment.dtype}")
+    b, p = assignment.shape
+    lb, o, k = picklist.shape
+    l = src.shape[1] if src.dim() == 3 else -1
+    want = (lb, l, 2) if locs is not None else (lb, l, l)
+    if src.dim() != 3 or tuple(src.shape) != want or lb == 0 or b % lb != 0:
+        raise ValueError(f"slap_local_search: {'locs' if locs is not None else 'distances'} of "
+                         f"shape {tuple(src.shape)} does not fit assignment "
+                         f"{tuple(assignment.shape)} and picklist {tuple(picklist.shape)}")
+    if not 1 <= p <= nat.SLAP_LS_MAX_PRODUCTS:
+        raise ValueError(f"slap_local_search: {p} products; the supported range is 1.."
+                         f"{nat.SLAP_LS_MAX_PRODUCTS}")
+    if not p <= l <= nat.SLAP_LS_MAX_SLOTS:
+        raise ValueError(f"slap_local_search: {l} slots cannot hold {p} products or exceed "
+                         f"the supported maximum {nat.SLAP_LS_MAX_SLOTS}")
+    if not 1 <= o * k <= 65536:
+        raise ValueError(f"slap_local_search: {o} orders of {k} picks; 1..65536 picks are "
+                         "supported")
+    src = src.contiguous().float()
+    picklist = picklist.contiguous()
+    if picklist.dtype != torch.int64:
+        picklist = picklist.long()
+    dtype, dev = assignment.dtype, assignment.device
+    assign = assignment.contiguous() if dtype == torch.int32 else assignment.to(torch.int32)
+    wild = None
+    if dtype == torch.int64:  # a slot beyond int32 must not wrap into range
+        wild = (assignment < -1) | (assignment > l)
+        assign = torch.where(wild, -1, assignment).to(torch.int32)
+    out = torch.empty((b, p), dtype=torch.int32, device=dev)
+    sweeps = torch.empty(b, dtype=torch.int32, device=dev) if return_sweeps else None
+    cost = torch.empty(b, dtype=torch.int64, device=dev) if return_cost else None
+
+    def result():
+        rows = out if dtype == torch.int32 else out.to(dtype)
+        if wild is not None:  # such a row failed its check: it comes back as it was
+            rows = torch.where(wild, assignment, rows)
+        res = tuple(x for x in (rows, sweeps, cost) if x is not None)
+        return res if len(res) > 1 else res[0]
+
+    if b == 0:
+        return result()
+    own = status is None
+    if own:
+        status = nat.scratch_status(dev)
+    args = (b, l, p, o, k, nat.ptr(src) if locs is not None else None,
+            nat.ptr(src) if locs is None else None, lb, nat.ptr(picklist), nat.ptr(assign),
+            int(max_iterations), nat.ptr(out), nat.ptr(sweeps), nat.ptr(cost))
+    if scheme == nat.SLAP_LS_AUTO:
+        nat.call("co_slap_local_search", *args, nat.ptr(status), nat.stream_of(assign))
+    else:
+        if dev.type == "cpu":
+            raise ValueError("slap_local_search: the host build has one evaluation scheme")
+        if scheme == nat.SLAP_LS_TABLE and not nat.slap_ls_table_fits(p, l):
+            raise ValueError(f"slap_local_search: the table of {p} products x {l} slots does "
+                             f"not fit the LDS budget of {nat.SLAP_LS_LDS_BYTES} bytes")
+        nat.call("co_slap_local_search_scheme", *args, int(scheme), nat.ptr(status),
+                 nat.stream_of(assign))
+    if own:
+        bits = int(status.item())
+        nat.release_status(status, (bits,))
+        if bits & nat.ST_INVALID_TOUR:
+            raise AssertionError("Invalid assignment")
+        if bits & nat.ST_INDEX_RANGE:
+            raise IndexError("index out of range in SLAP picklist")
+    return result()
+
+
 def get_num_starts(td, env_name=None):
     """``ops.py:126-136``."""
     n = td["action_mask"].shape[-1]
