@@ -238,26 +238,6 @@ __device__ __forceinline__ void grp_argmin_split(float& v, int& idx) {
 }
 
 // ---------------------------------------------------------------------------
-// The diagonal strip of the 2-opt moves (i, j), 1 <= i < j <= n-1, of a cyclic tour of n
-// positions (two_opt.hip describes the walk; cvrp_ls.hip walks it too).  Element c of strip
-// row q (0 <= c <= n): row q holds diagonal r = q + 1 (n - r elements, the closing one
-// included) and then diagonal n-1-r (r + 1 elements).  An odd middle diagonal (n-1)/2 ends
-// the strip as the first part of a last, half-filled row.  j == n marks a closing element.
-struct StripMove {
-  int i, j;
-};
-
-__device__ __forceinline__ StripMove strip_move(int q, int c, int n) {
-  const int r = q + 1, a = n - r;
-  const bool first = c < a;
-  const int d = first ? r : n - 1 - r, t = first ? c : c - a;
-  StripMove m;
-  m.i = 1 + t;
-  m.j = 1 + t + d;
-  return m;
-}
-
-// ---------------------------------------------------------------------------
 // The candidate order of the SLAP closest-free policy: u64 keys (distance key << 32 |
 // location), sorted ascending once per lane (slap_group_kernel, slap_closest_steps_kernel).
 //

@@ -32,14 +32,12 @@
 // Each lane keeps a running (change, key) minimum, key = kind << 30 | i << 16 | j, equal
 // changes going to the lower key (2-opt before relocate, then i, then j); one wave
 // reduction with the same rule gives the sweep's move.
-#include "co_common.hpp"
+#include "co_local_search.hpp"
 
 using namespace co;
 
 namespace {
 
-constexpr int kCoords = 0, kMatLds = 1, kMatGlobal = 2;
-constexpr int kStep = 63;  // strip positions a window advances by (64 lanes, one shared)
 constexpr int kRelocate = 1 << 30;
 
 static_assert(4 * (CO_CVRP_LS_STAGE_N + 1) * (CO_CVRP_LS_STAGE_N + 1) +
@@ -94,8 +92,7 @@ __global__ __launch_bounds__(64) void cvrp_ls_kernel(
         bad = true;
       } else if (a > 0) {
         ++customers;
-        const uint32_t bit = 1u << (a & 31);
-        if (atomicOr(&bits[a >> 5], bit) & bit) bad = true;
+        if (mark_once(bits, a)) bad = true;
       }
     }
     for (int c = lane; c < N; c += 64) bad |= !in_range(drow[c]);
@@ -137,16 +134,7 @@ __global__ __launch_bounds__(64) void cvrp_ls_kernel(
     __syncthreads();
     const int64_t cap_q = quantise(cap) + (int64_t(1) << 20);
     // D[g[ka], g[kb]] for tour positions ka, kb <= m
-    auto dist = [&](int ka, int kb) -> float {
-      if constexpr (MODE == kCoords) {
-        const float2 p = P[ka], q = P[kb];
-        return edge_len(p.x, p.y, q.x, q.y);
-      } else if constexpr (MODE == kMatLds) {
-        return Dl[g[ka] * V + g[kb]];
-      } else {
-        return Dg[g[ka] * V + g[kb]];
-      }
-    };
+    const TourDist<MODE> dist{P, g, MODE == kMatLds ? Dl : Dg, V};
     // E, R, head, tail, PZ from g, P, Q (all of them: O(m))
     auto rebuild = [&]() {
       for (int k = lane; k < m; k += 64) E[k] = dist(k == 0 ? m - 1 : k - 1, k);
@@ -208,48 +196,33 @@ __global__ __launch_bounds__(64) void cvrp_ls_kernel(
         R[k] = (dist(k - 1, k + 1) - E[k]) - E[k + 1 == m ? 0 : k + 1];
       __syncthreads();
     };
-    // the strips' per-lane start and window step: (m-2)(m+1)/2 2-opt elements and
-    // (m-1)(m+1) relocate elements, both in rows of m + 1
-    const int width = m + 1;
+    // the strips: (m-2)(m+1)/2 2-opt elements and (m-1)(m+1) relocate elements, both in
+    // rows of m + 1
     const int total2 = (m - 2) * (m + 1) / 2, total_r = (m - 1) * (m + 1);
-    const int q0 = lane / width, c0 = lane - q0 * width;
-    const int step_q = kStep / width, step_c = kStep - step_q * width;
+    const StripCursor start(lane, m + 1);
     int it = 0;
     while (it < max_it) {
       rebuild();
       float best = 0.f;  // only a change < 0 counts
       int bkey = 0x7fffffff;
-      int q = q0, c = c0;
+      StripCursor cur = start;
       // every lane runs every window (the lane exchange needs the whole wave); a strip's
       // last element is a closing one, so its last candidate is at total - 2
       for (int x0 = 0; x0 < total2 - 1; x0 += kStep) {  // m < 3: no 2-opt move
-        const bool live = x0 + lane < total2;
-        const StripMove mv = strip_move(live ? q : 0, live ? c : 0, m);  // idle lanes: move (1, 2)
-        const float d = dist(mv.i - 1, mv.j);
-        // D[g[i], g[j+1]] is the successor's d: DPP wave_shl:1, lane l reads lane l + 1
-        const float d_next = __uint_as_float(dpp_u<0x130>(__float_as_uint(d)));
-        const int jn = mv.j + 1 >= m ? 0 : mv.j + 1;
-        const float change = ((d + d_next) - E[mv.i]) - E[jn];
-        const int key = (mv.i << 16) | mv.j;
-        const bool mine = live & (lane < kStep) & (mv.j < m);
-        if (mine & ((change < best) | ((change == best) & (key < bkey)))) {
+        const TwoOptCandidate mv = two_opt_candidate(cur, x0 + lane < total2, lane, m, E, dist);
+        if (mv.mine & ((mv.change < best) | ((mv.change == best) & (mv.key < bkey)))) {
           // a depot inside g[i..j]: both new boundary routes must fit
           const bool ok = PZ[mv.j] < mv.i || (head[mv.i - 1] + head[mv.j] <= cap_q &&
                                               tail[mv.i] + tail[mv.j + 1] <= cap_q);
-          best = ok ? change : best;
-          bkey = ok ? key : bkey;
+          best = ok ? mv.change : best;
+          bkey = ok ? mv.key : bkey;
         }
-        q += step_q;
-        c += step_c;
-        if (c >= width) {
-          c -= width;
-          ++q;
-        }
+        cur.advance();
       }
-      q = q0, c = c0;
+      cur = start;
       for (int x0 = 0; x0 < total_r - 1; x0 += kStep) {
         const bool live = x0 + lane < total_r;
-        const int i = live ? 1 + q : 1, j = live ? c : 0;  // j == m: the closing element
+        const int i = live ? 1 + cur.q : 1, j = live ? cur.c : 0;  // j == m: the closing element
         const float d = dist(j, i);                        // D[a, c]
         float d_next;                                      // D[c, b]
         if constexpr (MODE == kCoords)
@@ -266,12 +239,7 @@ __global__ __launch_bounds__(64) void cvrp_ls_kernel(
           best = ok ? change : best;
           bkey = ok ? key : bkey;
         }
-        q += step_q;
-        c += step_c;
-        if (c >= width) {
-          c -= width;
-          ++q;
-        }
+        cur.advance();
       }
       grp_argmin_split<64>(best, bkey);
       best = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(best)));
@@ -281,20 +249,8 @@ __global__ __launch_bounds__(64) void cvrp_ls_kernel(
       const int p = (bkey >> 16) & 0x3fff, r = bkey & 0xffff;
       __syncthreads();
       if (!(bkey & kRelocate)) {  // reverse g[p..r]
-        for (int t = lane; t < ((r - p + 1) >> 1); t += 64) {
-          const int u = p + t, v = r - t;
-          const int gu = g[u];
-          g[u] = g[v];
-          g[v] = gu;
-          const int64_t qu = Q[u];
-          Q[u] = Q[v];
-          Q[v] = qu;
-          if constexpr (MODE == kCoords) {
-            const float2 pu = P[u];
-            P[u] = P[v];
-            P[v] = pu;
-          }
-        }
+        if constexpr (MODE == kCoords) reverse_segment(lane, p, r, g, Q, P);
+        else reverse_segment(lane, p, r, g, Q);
       } else {  // g[p] goes between positions r and r + 1: the positions between shift by one
         const int cg = g[p];
         const int64_t cq = Q[p];
@@ -355,21 +311,17 @@ extern "C" int co_cvrp_local_search(int64_t B, int64_t N, int64_t T, const float
                                     const int64_t* actions, int64_t sb, int64_t st,
                                     int64_t max_iterations, int64_t* actions_out,
                                     int32_t* sweeps_out, int32_t* status, void* stream) {
-  if (B < 0 || N < 1 || T < N) return CO_E_INVAL;
+  if (N < 1 || T < N) return CO_E_INVAL;
   const int64_t len = (T < 2 * N ? T : 2 * N) + 1;  // the longest giant tour
   if (len > CO_CVRP_LS_MAX_LEN) return CO_E_INVAL;
-  if (locs_batch <= 0 || (B > 0 && B % locs_batch != 0)) return CO_E_INVAL;
-  if (B == 0) return CO_OK;
-  if ((locs == nullptr) == (distances == nullptr)) return CO_E_INVAL;
-  if (!demand || !actions || !actions_out || actions_out == actions || !status)
-    return CO_E_INVAL;
-  if ((reinterpret_cast<uintptr_t>(locs) & 7) || (reinterpret_cast<uintptr_t>(distances) & 3) ||
-      (reinterpret_cast<uintptr_t>(demand) & 3) || (reinterpret_cast<uintptr_t>(capacity) & 3))
-    return CO_E_ALIGN;
+  const int rc = check_search_args(
+      B, locs_batch, locs, distances,
+      demand && actions && actions_out && actions_out != actions && status,
+      !((reinterpret_cast<uintptr_t>(demand) | reinterpret_cast<uintptr_t>(capacity)) & 3));
+  if (rc != CO_OK || B == 0) return rc;
   const int n = (int)N, steps = (int)T, slots = (int)len + 1;  // + the sentinel
-  const int max_it = max_iterations > INT32_MAX ? INT32_MAX
-                                                : max_iterations < 0 ? 0 : (int)max_iterations;
-  const dim3 grid((unsigned)(B < (1 << 22) ? B : (1 << 22)));  // rows beyond it: grid-stride
+  const int max_it = clamp_iterations(max_iterations);
+  const dim3 grid = row_grid(B);
   hipStream_t s = (hipStream_t)stream;
 #define CO_CVRP_LS(MODE, SRC, LDS)                                                              \
   hipLaunchKernelGGL(cvrp_ls_kernel<MODE>, grid, dim3(64), (size_t)(LDS), s, B, n, steps,       \

@@ -35,6 +35,34 @@ inline float edge_len(float x0, float y0, float x1, float y1) {
   return std::sqrt(dx * dx + dy * dy);  // torch.norm(p=2) over 2 elements, no FMA
 }
 
+// ---- what the three local searches' entry points share (the searches themselves do not)
+inline int64_t ls_clamp_iterations(int64_t max_iterations) {
+  return max_iterations > INT32_MAX ? INT32_MAX : max_iterations;
+}
+
+// the batch (B == 0 is CO_OK: the caller returns), exactly one distance source and the
+// entry point's other required pointers
+inline int ls_check_args(int64_t B, int64_t LB, const float* locs, const float* distances,
+                         bool others_given) {
+  if (B < 0 || LB <= 0 || (B > 0 && B % LB != 0)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if ((locs == nullptr) == (distances == nullptr) || !others_given) return CO_E_INVAL;
+  return CO_OK;
+}
+
+// D[a][c] of instance `inst` of V nodes: its matrix when one is given, else from its
+// coordinates
+struct LsDist {
+  const float *lr, *dm;
+  int64_t V;
+  LsDist(const float* locs, const float* distances, int64_t inst, int64_t V_)
+      : lr(locs ? locs + inst * V_ * 2 : nullptr),
+        dm(distances ? distances + inst * V_ * V_ : nullptr), V(V_) {}
+  float operator()(int64_t a, int64_t c) const {
+    return dm ? dm[a * V + c] : edge_len(lr[2 * a], lr[2 * a + 1], lr[2 * c], lr[2 * c + 1]);
+  }
+};
+
 // ---- SLEEF xexpf (u10, FMA) / xlogf_u1 (FMA), as ATen's vectorised CPU kernels call them
 float aten_expf(float d) {
   const float qf = std::nearbyint(d * 1.442695040888963407359924681001892137426645954152985934135449406931f);
@@ -254,13 +282,12 @@ CO_HOST_API int co_tsp_two_opt(int64_t B, int64_t N, const float* locs, const fl
                                int64_t LB, const int64_t* actions, int64_t sb, int64_t st,
                                int64_t max_iterations, int64_t* actions_out,
                                int32_t* sweeps_out, int32_t* status, void*) {
-  if (B < 0 || N <= 0 || N > CO_TWO_OPT_MAX_N) return CO_E_INVAL;
-  if (LB <= 0 || (B > 0 && B % LB != 0)) return CO_E_INVAL;
-  if (B == 0) return CO_OK;
-  if ((locs == nullptr) == (distances == nullptr)) return CO_E_INVAL;
-  if (!actions || !actions_out || actions_out == actions || !status) return CO_E_INVAL;
+  if (N <= 0 || N > CO_TWO_OPT_MAX_N) return CO_E_INVAL;
+  const int rc = ls_check_args(B, LB, locs, distances,
+                               actions && actions_out && actions_out != actions && status);
+  if (rc != CO_OK || B == 0) return rc;
   const int64_t n = N;
-  const int64_t max_it = max_iterations > INT32_MAX ? INT32_MAX : max_iterations;
+  const int64_t max_it = ls_clamp_iterations(max_iterations);
   std::vector<int64_t> tour((size_t)n);
   std::vector<uint8_t> seen((size_t)n);
   for (int64_t b = 0; b < B; ++b) {
@@ -280,11 +307,7 @@ CO_HOST_API int co_tsp_two_opt(int64_t B, int64_t N, const float* locs, const fl
       set_status(status, CO_ST_INVALID_TOUR);
       continue;
     }
-    const float* lr = locs ? locs + (b % LB) * n * 2 : nullptr;
-    const float* dm = distances ? distances + (b % LB) * n * n : nullptr;
-    auto D = [&](int64_t a, int64_t c) -> float {
-      return dm ? dm[a * n + c] : edge_len(lr[2 * a], lr[2 * a + 1], lr[2 * c], lr[2 * c + 1]);
-    };
+    const LsDist D(locs, distances, b % LB, n);
     double min_change = -1.0;
     int64_t it = 0;
     while (min_change < -1e-6 && it < max_it) {
@@ -509,15 +532,13 @@ CO_HOST_API int co_cvrp_local_search(int64_t B, int64_t N, int64_t T, const floa
                                      int64_t sb, int64_t st, int64_t max_iterations,
                                      int64_t* actions_out, int32_t* sweeps_out, int32_t* status,
                                      void*) {
-  if (B < 0 || N < 1 || T < N) return CO_E_INVAL;
+  if (N < 1 || T < N) return CO_E_INVAL;
   if ((T < 2 * N ? T : 2 * N) + 1 > CO_CVRP_LS_MAX_LEN) return CO_E_INVAL;
-  if (LB <= 0 || (B > 0 && B % LB != 0)) return CO_E_INVAL;
-  if (B == 0) return CO_OK;
-  if ((locs == nullptr) == (distances == nullptr)) return CO_E_INVAL;
-  if (!demand || !actions || !actions_out || actions_out == actions || !status)
-    return CO_E_INVAL;
+  const int rc = ls_check_args(
+      B, LB, locs, distances, demand && actions && actions_out && actions_out != actions && status);
+  if (rc != CO_OK || B == 0) return rc;
   const int64_t V = N + 1;  // nodes, depot first
-  const int64_t max_it = max_iterations > INT32_MAX ? INT32_MAX : max_iterations;
+  const int64_t max_it = ls_clamp_iterations(max_iterations);
   GiantTour gt;
   gt.q.assign((size_t)V, 0);
   std::vector<uint8_t> seen((size_t)V);
@@ -554,11 +575,7 @@ CO_HOST_API int co_cvrp_local_search(int64_t B, int64_t N, int64_t T, const floa
     if (gt.g.size() > 1 && gt.g.back() == 0) gt.g.pop_back();
     const int64_t m = gt.m = (int64_t)gt.g.size();
     const int64_t cap_q = cvrp_ls_q(cap) + (int64_t(1) << 20);
-    const float* lr = locs ? locs + inst * V * 2 : nullptr;
-    const float* dm = distances ? distances + inst * V * V : nullptr;
-    auto D = [&](int64_t a, int64_t c) -> float {
-      return dm ? dm[a * V + c] : edge_len(lr[2 * a], lr[2 * a + 1], lr[2 * c], lr[2 * c + 1]);
-    };
+    const LsDist D(locs, distances, inst, V);
     std::vector<int64_t>& g = gt.g;
     int64_t it = 0;
     while (it < max_it) {
@@ -721,15 +738,14 @@ CO_HOST_API int co_slap_local_search(int64_t B, int64_t L, int64_t P, int64_t O,
                                      int64_t max_iterations, int32_t* assign_out,
                                      int32_t* sweeps_out, int64_t* cost_out, int32_t* status,
                                      void*) {
-  if (B < 0 || P < 1 || P > CO_SLAP_LS_MAX_PRODUCTS || L < P || L > CO_SLAP_LS_MAX_SLOTS)
+  if (P < 1 || P > CO_SLAP_LS_MAX_PRODUCTS || L < P || L > CO_SLAP_LS_MAX_SLOTS)
     return CO_E_INVAL;
   if (O < 1 || K < 1 || O > 65536 || K > 65536 || O * K > 65536) return CO_E_INVAL;
-  if (LB <= 0 || (B > 0 && B % LB != 0)) return CO_E_INVAL;
-  if (B == 0) return CO_OK;
-  if ((locs == nullptr) == (distances == nullptr)) return CO_E_INVAL;
-  if (!picklist || !assignment || !assign_out || assign_out == assignment || !status)
-    return CO_E_INVAL;
-  const int64_t max_it = max_iterations > INT32_MAX ? INT32_MAX : max_iterations;
+  const int rc = ls_check_args(
+      B, LB, locs, distances,
+      picklist && assignment && assign_out && assign_out != assignment && status);
+  if (rc != CO_OK || B == 0) return rc;
+  const int64_t max_it = ls_clamp_iterations(max_iterations);
   std::vector<int64_t> W((size_t)(P * P)), C((size_t)(P * L)), s((size_t)P), dcol((size_t)L),
       drow((size_t)L);
   std::vector<uint8_t> occ((size_t)L);
@@ -738,8 +754,8 @@ CO_HOST_API int co_slap_local_search(int64_t B, int64_t L, int64_t P, int64_t O,
     int32_t* out = assign_out + b * P;
     const int64_t inst = b % LB;
     const int64_t* pl = picklist + inst * O * K;
-    const float* lr = locs ? locs + inst * L * 2 : nullptr;
-    const float* dm = distances ? distances + inst * L * L : nullptr;
+    const LsDist D(locs, distances, inst, L);
+    const float *lr = D.lr, *dm = D.dm;
     bool bad = false, bad_pl = false;
     std::fill(occ.begin(), occ.end(), 0);
     for (int64_t p = 0; p < P; ++p) {
@@ -770,9 +786,7 @@ CO_HOST_API int co_slap_local_search(int64_t B, int64_t L, int64_t P, int64_t O,
       continue;
     }
     auto Q = [&](int64_t u, int64_t v) -> int64_t {
-      const float d = dm ? dm[u * L + v]
-                         : edge_len(lr[2 * u], lr[2 * u + 1], lr[2 * v], lr[2 * v + 1]);
-      return (int64_t)std::llrint((double)d * 1048576.0);  // 2^20
+      return (int64_t)std::llrint((double)D(u, v) * 1048576.0);  // 2^20
     };
     for (int64_t p = 0; p < P; ++p)
       for (int64_t l = 0; l < L; ++l) {

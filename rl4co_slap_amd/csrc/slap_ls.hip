@@ -28,13 +28,13 @@
 // lane meets its candidates in ascending key order (kind << 30 | p << 16 | x), so a strict
 // `<` keeps the lowest key of equal changes; the wave reduction is an int64 min and then
 // the min key among the lanes that hold it.
-#include "co_common.hpp"
+#include "co_local_search.hpp"
 
 using namespace co;
 
 namespace {
 
-constexpr int kCoords = 0, kMatrix = 1;
+constexpr int kMatrix = 1;  // beside kCoords: a matrix, read through L2
 constexpr int kSwap = 1 << 30;
 
 constexpr int round8(int x) { return (x + 7) & ~7; }
@@ -98,8 +98,7 @@ __global__ __launch_bounds__(64) void slap_ls_kernel(
         bad = true;
       } else {
         s[p] = v;
-        const uint32_t bit = 1u << (v & 31);
-        if (atomicOr(&occ[v >> 5], bit) & bit) bad = true;
+        if (mark_once(occ, v)) bad = true;
       }
     }
     for (int idx = lane; idx < OK; idx += 64) {
@@ -298,27 +297,23 @@ extern "C" int co_slap_local_search_scheme(int64_t B, int64_t L, int64_t P, int6
                                            int32_t* assign_out, int32_t* sweeps_out,
                                            int64_t* cost_out, int32_t scheme, int32_t* status,
                                            void* stream) {
-  if (B < 0 || P < 1 || P > CO_SLAP_LS_MAX_PRODUCTS || L < P || L > CO_SLAP_LS_MAX_SLOTS)
+  if (P < 1 || P > CO_SLAP_LS_MAX_PRODUCTS || L < P || L > CO_SLAP_LS_MAX_SLOTS)
     return CO_E_INVAL;
   if (O < 1 || K < 1 || O > 65536 || K > 65536 || O * K > 65536) return CO_E_INVAL;
-  if (locs_batch <= 0 || (B > 0 && B % locs_batch != 0)) return CO_E_INVAL;
   if (scheme != CO_SLAP_LS_AUTO && scheme != CO_SLAP_LS_DIRECT && scheme != CO_SLAP_LS_TABLE)
     return CO_E_INVAL;
   const bool fits = CO_SLAP_LS_TABLE_FITS(P, L);
   if (scheme == CO_SLAP_LS_TABLE && !fits) return CO_E_INVAL;
-  if (B == 0) return CO_OK;
-  if ((locs == nullptr) == (distances == nullptr)) return CO_E_INVAL;
-  if (!picklist || !assignment || !assign_out || assign_out == assignment || !status)
-    return CO_E_INVAL;
-  if ((reinterpret_cast<uintptr_t>(locs) & 7) || (reinterpret_cast<uintptr_t>(distances) & 3) ||
-      (reinterpret_cast<uintptr_t>(picklist) & 7) || (reinterpret_cast<uintptr_t>(cost_out) & 7))
-    return CO_E_ALIGN;
+  const int rc = check_search_args(
+      B, locs_batch, locs, distances,
+      picklist && assignment && assign_out && assign_out != assignment && status,
+      !((reinterpret_cast<uintptr_t>(picklist) | reinterpret_cast<uintptr_t>(cost_out)) & 7));
+  if (rc != CO_OK || B == 0) return rc;
   const bool table = scheme == CO_SLAP_LS_TABLE || (scheme == CO_SLAP_LS_AUTO && fits);
   const int p = (int)P, l = (int)L, ok = (int)(O * K), k = (int)K;
-  const int max_it = max_iterations > INT32_MAX ? INT32_MAX
-                                                : max_iterations < 0 ? 0 : (int)max_iterations;
+  const int max_it = clamp_iterations(max_iterations);
   if (lds_bytes(p, l, kCoords, table) > CO_SLAP_LS_LDS_BYTES) return CO_E_INVAL;  // cannot be
-  const dim3 grid((unsigned)(B < (1 << 22) ? B : (1 << 22)));  // rows beyond it: grid-stride
+  const dim3 grid = row_grid(B);
   hipStream_t s = (hipStream_t)stream;
 #define CO_SLAP_LS(MODE, TABLE, SRC)                                                           \
   hipLaunchKernelGGL((slap_ls_kernel<MODE, TABLE>), grid, dim3(64),                            \

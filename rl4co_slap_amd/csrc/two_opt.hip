@@ -25,14 +25,11 @@
 // going to the lower key (the reference's ascending scan with a strict `<`); one wave
 // reduction with the same rule gives the sweep's move.  After the reversal of tour[i..j]
 // (and P[i..j]) only E[i..j+1] is recomputed, in the new (row, column) orientation.
-#include "co_common.hpp"
+#include "co_local_search.hpp"
 
 using namespace co;
 
 namespace {
-
-constexpr int kCoords = 0, kMatLds = 1, kMatGlobal = 2;
-constexpr int kStep = 63;  // strip positions a window advances by (64 lanes, one shared)
 
 static_assert(4 * CO_TWO_OPT_STAGE_N * CO_TWO_OPT_STAGE_N + 8 * (CO_TWO_OPT_STAGE_N + 1) <=
                   64 * 1024,
@@ -51,11 +48,9 @@ __global__ __launch_bounds__(64) void two_opt_kernel(
   [[maybe_unused]] float2* P = reinterpret_cast<float2*>(s_raw + 8 * (n + 1));  // kCoords: n + 1
   [[maybe_unused]] float* Dl = reinterpret_cast<float*>(s_raw + 8 * (n + 1));   // kMatLds: n * n
   const int lane = threadIdx.x;
-  // the strip: (n-2)(n+1)/2 elements in rows of n+1; this lane's first element and the
-  // (row, column) step of one window
-  const int width = n + 1, total = (n - 2) * (n + 1) / 2;
-  const int q0 = lane / width, c0 = lane - q0 * width;
-  const int step_q = kStep / width, step_c = kStep - step_q * width;
+  // the strip: (n-2)(n+1)/2 elements in rows of n+1
+  const int total = (n - 2) * (n + 1) / 2;
+  const StripCursor start(lane, n + 1);
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     const int64_t* arow = actions + b * sb;
     int64_t* orow = out + b * (int64_t)n;
@@ -69,8 +64,7 @@ __global__ __launch_bounds__(64) void two_opt_kernel(
         bad = true;
       } else {
         tour[k] = (int)a;
-        const uint32_t bit = 1u << (a & 31);
-        if (atomicOr(&bits[a >> 5], bit) & bit) bad = true;
+        if (mark_once(bits, a)) bad = true;
       }
     }
     bad = __any(bad);
@@ -93,45 +87,23 @@ __global__ __launch_bounds__(64) void two_opt_kernel(
     }
     __syncthreads();
     // D[tour[ka], tour[kb]] for tour positions ka, kb (position n is position 0)
-    auto dist = [&](int ka, int kb) -> float {
-      if constexpr (MODE == kCoords) {
-        const float2 p = P[ka], q = P[kb];
-        return edge_len(p.x, p.y, q.x, q.y);
-      } else if constexpr (MODE == kMatLds) {
-        return Dl[tour[ka] * n + tour[kb]];
-      } else {
-        return Dg[tour[ka] * n + tour[kb]];
-      }
-    };
+    const TourDist<MODE> dist{P, tour, MODE == kMatLds ? Dl : Dg, n};
     for (int k = lane; k < n; k += 64) E[k] = dist(k == 0 ? n - 1 : k - 1, k);
     __syncthreads();
     int it = 0;
     while (it < max_it) {
       float best = 0.f;  // the reference's delta = 0 with a strict `<`
       int bkey = 0x7fffffff;
-      int q = q0, c = c0;
+      StripCursor cur = start;
       // every lane runs every window (the lane exchange needs the whole wave); the strip's
       // last element is a closing one, so the last move is at total - 2
       for (int x0 = 0; x0 < total - 1; x0 += kStep) {
-        const bool live = x0 + lane < total;
-        const StripMove m = strip_move(live ? q : 0, live ? c : 0, n);  // idle lanes: move (1, 2)
-        const float g = dist(m.i - 1, m.j);
-        // D[t[i], t[j+1]] is the successor's g: DPP wave_shl:1, lane l reads lane l + 1
-        // (lane 63 reads 0 and owns no move)
-        const float g_next = __uint_as_float(dpp_u<0x130>(__float_as_uint(g)));
-        const int jn = m.j + 1 >= n ? 0 : m.j + 1;
-        const float change = ((g + g_next) - E[m.i]) - E[jn];
-        const int key = (m.i << 16) | m.j;
-        const bool mine = live & (lane < kStep) & (m.j < n);
-        const bool take = mine & ((change < best) | ((change == best) & (key < bkey)));
-        best = take ? change : best;
-        bkey = take ? key : bkey;
-        q += step_q;
-        c += step_c;
-        if (c >= width) {
-          c -= width;
-          ++q;
-        }
+        const TwoOptCandidate m = two_opt_candidate(cur, x0 + lane < total, lane, n, E, dist);
+        const bool take =
+            m.mine & ((m.change < best) | ((m.change == best) & (m.key < bkey)));
+        best = take ? m.change : best;
+        bkey = take ? m.key : bkey;
+        cur.advance();
       }
       grp_argmin_split<64>(best, bkey);
       best = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(best)));
@@ -139,17 +111,8 @@ __global__ __launch_bounds__(64) void two_opt_kernel(
       ++it;
       if (!((double)best < -1e-6)) break;  // min_change = 0: the search ends
       const int p = bkey >> 16, r = bkey & 0xffff;  // reverse tour[p..r]
-      for (int t = lane; t < ((r - p + 1) >> 1); t += 64) {
-        const int u = p + t, v = r - t;
-        const int tu = tour[u];
-        tour[u] = tour[v];
-        tour[v] = tu;
-        if constexpr (MODE == kCoords) {
-          const float2 pu = P[u];
-          P[u] = P[v];
-          P[v] = pu;
-        }
-      }
+      if constexpr (MODE == kCoords) reverse_segment(lane, p, r, tour, P);
+      else reverse_segment(lane, p, r, tour);
       __syncthreads();
       for (int k = p + lane; k <= r + 1; k += 64) {
         const int kk = k == n ? 0 : k;
@@ -168,17 +131,13 @@ extern "C" int co_tsp_two_opt(int64_t B, int64_t N, const float* locs, const flo
                               int64_t locs_batch, const int64_t* actions, int64_t sb, int64_t st,
                               int64_t max_iterations, int64_t* actions_out, int32_t* sweeps_out,
                               int32_t* status, void* stream) {
-  if (B < 0 || N <= 0 || N > CO_TWO_OPT_MAX_N) return CO_E_INVAL;
-  if (locs_batch <= 0 || (B > 0 && B % locs_batch != 0)) return CO_E_INVAL;
-  if (B == 0) return CO_OK;
-  if ((locs == nullptr) == (distances == nullptr)) return CO_E_INVAL;
-  if (!actions || !actions_out || actions_out == actions || !status) return CO_E_INVAL;
-  if ((reinterpret_cast<uintptr_t>(locs) & 7) || (reinterpret_cast<uintptr_t>(distances) & 3))
-    return CO_E_ALIGN;
-  const int n = (int)N;
-  const int max_it = max_iterations > INT32_MAX ? INT32_MAX
-                                                : max_iterations < 0 ? 0 : (int)max_iterations;
-  const dim3 grid((unsigned)(B < (1 << 22) ? B : (1 << 22)));  // rows beyond it: grid-stride
+  if (N <= 0 || N > CO_TWO_OPT_MAX_N) return CO_E_INVAL;
+  const int rc = check_search_args(
+      B, locs_batch, locs, distances,
+      actions && actions_out && actions_out != actions && status, true);
+  if (rc != CO_OK || B == 0) return rc;
+  const int n = (int)N, max_it = clamp_iterations(max_iterations);
+  const dim3 grid = row_grid(B);
   hipStream_t s = (hipStream_t)stream;
   const int state = 8 * (n + 1);  // tour + edge terms
 #define CO_TWO_OPT(MODE, SRC, LDS)                                                              \

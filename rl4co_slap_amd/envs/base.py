@@ -24,7 +24,7 @@ from typing import Iterable, Optional
 import torch
 
 from .. import _native as nat
-from ..td import TensorDict
+from ..td import RepeatedRows, TensorDict
 from ..utils.ops import get_num_starts, select_start_nodes
 from ..utils.pool import OutputPool
 
@@ -146,6 +146,19 @@ class RL4COEnvBase(metaclass=abc.ABCMeta):
 
     def local_search(self, td, actions, **kwargs):
         raise NotImplementedError(f"Local is not implemented yet for {self.name} environment")
+
+    @staticmethod
+    def _instance_entries(td, keys):
+        """The td entries under ``keys`` as a batched search reads them (an absent key gives
+        None): a multistart td's un-replicated rows (every entry a ``RepeatedRows`` with the
+        same repeat count: the search's ``b % LB`` indexing reads them in place), else
+        materialised tensors."""
+        raw_get = td.get_raw if hasattr(td, "get_raw") else td.get
+        raws = [raw_get(k, None) for k in keys]
+        if all(isinstance(r, RepeatedRows) for r in raws) \
+                and len({r.repeats for r in raws}) == 1:
+            return [r.source() for r in raws]
+        return [r.materialize() if isinstance(r, RepeatedRows) else r for r in raws]
 
     # -- datasets (base.py:236-286) --------------------------------------------
     def dataset(self, batch_size=[], phase="train", filename=None):

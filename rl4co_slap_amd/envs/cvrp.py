@@ -7,7 +7,7 @@ import torch
 from torch.distributions import Uniform
 
 from .. import _native as nat
-from ..td import RepeatedRows, TensorDict, set_many
+from ..td import TensorDict, set_many
 from .base import RL4COEnvBase
 from .common import Generator, device_uniform, get_sampler
 
@@ -287,19 +287,10 @@ class CVRPEnv(RL4COEnvBase):
         unknown = set(reference_kwargs) - self._REFERENCE_LS_KWARGS
         if unknown:
             raise TypeError(f"improve() got an unexpected keyword argument {sorted(unknown)[0]!r}")
-        raw_get = td.get_raw if hasattr(td, "get_raw") else td.get
-        dist = raw_get("distances", None)
-        raws = [dist if dist is not None else raw_get("locs"), raw_get("demand"),
-                raw_get("vehicle_capacity")]
-        if all(isinstance(r, RepeatedRows) for r in raws) \
-                and len({r.repeats for r in raws}) == 1:
-            src, demand, vcap = (r.source() for r in raws)
-        else:
-            src, demand, vcap = (r.materialize() if isinstance(r, RepeatedRows) else r
-                                 for r in raws)
+        key = "locs" if self._instance_entries(td, ["distances"])[0] is None else "distances"
+        src, demand, vcap = self._instance_entries(td, [key, "demand", "vehicle_capacity"])
         status = self.status_word(actions.device)
-        res = cvrp_local_search(actions, demand, locs=None if dist is not None else src,
-                                distances=src if dist is not None else None, capacity=vcap,
+        res = cvrp_local_search(actions, demand, **{key: src}, capacity=vcap,
                                 max_iterations=max_iterations, return_sweeps=return_sweeps,
                                 status=status)
         self.raise_for_status(status, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])

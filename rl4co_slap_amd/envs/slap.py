@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .. import _native as nat
-from ..td import RepeatedRows, TensorDict, set_many
+from ..td import TensorDict, set_many
 from .base import RL4COEnvBase
 from .common import Generator, device_uniform
 
@@ -294,14 +294,8 @@ class SLAPEnv(RL4COEnvBase):
 
         if metric not in ("euclidean", "dist_mat"):
             raise ValueError(f"improve: metric must be 'euclidean' or 'dist_mat', got {metric!r}")
-        raw_get = td.get_raw if hasattr(td, "get_raw") else td.get
         key = "locs" if metric == "euclidean" else "dist_mat"
-        raws = [raw_get(key), raw_get("picklist")]
-        if all(isinstance(r, RepeatedRows) for r in raws) \
-                and len({r.repeats for r in raws}) == 1:
-            src, picklist = (r.source() for r in raws)
-        else:
-            src, picklist = (r.materialize() if isinstance(r, RepeatedRows) else r for r in raws)
+        src, picklist = self._instance_entries(td, [key, "picklist"])
         assign = td["assignment"] if actions is None else actions
         status = self.status_word(assign.device)
         res = slap_local_search(assign, picklist, locs=src if metric == "euclidean" else None,

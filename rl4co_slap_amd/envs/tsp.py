@@ -228,13 +228,10 @@ class TSPEnv(RL4COEnvBase):
         reference does not check)."""
         from ..utils.ops import two_opt
 
-        raw_get = td.get_raw if hasattr(td, "get_raw") else td.get
-        dist = raw_get("distances", None)
-        raw = dist if dist is not None else raw_get("locs")
-        src = raw.source() if isinstance(raw, RepeatedRows) else raw
+        dist, = self._instance_entries(td, ["distances"])
+        locs, = self._instance_entries(td, ["locs"]) if dist is None else (None,)
         status = self.status_word(actions.device)
-        res = two_opt(actions, locs=None if dist is not None else src,
-                      distances=src if dist is not None else None,
+        res = two_opt(actions, locs=locs, distances=dist,
                       max_iterations=max_iterations, return_sweeps=return_sweeps,
                       status=status)
         self.raise_for_status(status, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])

@@ -163,6 +163,49 @@ def get_distance_matrix(locs: Tensor) -> Tensor:
     return out.reshape(*lead, n, n)
 
 
+# -- what the batched local searches (two_opt, cvrp_local_search, slap_local_search) share --
+
+def _pick_source(name, locs, distances):
+    """Exactly one of ``locs`` and ``distances``: (the tensor, its argument's name)."""
+    if (locs is None) == (distances is None):
+        raise ValueError(f"{name}: give exactly one of locs and distances")
+    return (locs, "locs") if locs is not None else (distances, "distances")
+
+
+def _fit_source(name, src, which, lb, nodes, b, fits):
+    """``src`` must be ``locs [lb, nodes, 2]`` or ``distances [lb, nodes, nodes]`` with
+    ``lb > 0`` dividing the ``b`` rows.  Returns it contiguous in f32 and the C ABI's
+    ``(locs, distances)`` pointer pair."""
+    want = (lb, nodes, 2) if which == "locs" else (lb, nodes, nodes)
+    if tuple(src.shape) != want or lb == 0 or b % lb != 0:
+        raise ValueError(f"{name}: {which} of shape {tuple(src.shape)} does not fit {fits}")
+    src = src.contiguous().float()
+    return src, ((nat.ptr(src), None) if which == "locs" else (None, nat.ptr(src)))
+
+
+def _search_outputs(shape, dtype, device, return_sweeps):
+    """The rows ``[B, ...]`` and, if asked for, the sweeps per row (int32 ``[B]``)."""
+    out = torch.empty(shape, dtype=dtype, device=device)
+    sweeps = torch.empty(shape[0], dtype=torch.int32, device=device) if return_sweeps else None
+    return out, sweeps
+
+
+def _run_with_status(launch, status, device, messages):
+    """``launch(status)`` on the caller's status word -- the caller reads it -- or on a
+    scratch word of this call's own, read (one host sync) and raised from by ``messages``:
+    ``(bit, exception, message)`` as ``RL4COEnvBase.raise_for_status`` takes them."""
+    if status is not None:
+        launch(status)
+        return
+    status = nat.scratch_status(device)
+    launch(status)
+    bits = int(status.item())
+    nat.release_status(status, (bits,))
+    for bit, exc, msg in messages:
+        if bits & bit:
+            raise exc(msg)
+
+
 def two_opt(actions: Tensor, locs: Tensor = None, distances: Tensor = None,
             max_iterations: int = 1000, return_sweeps: bool = False, status: Tensor = None):
     """``tsp/local_search.py:14-74`` on ``co_tsp_two_opt``: best-improvement 2-opt on every
@@ -173,9 +216,7 @@ def two_opt(actions: Tensor, locs: Tensor = None, distances: Tensor = None,
     with ``return_sweeps`` also the sweeps executed per row (int32 ``[B]``).  A row that is
     not a permutation raises ``AssertionError("Invalid tour")`` -- or, with a caller-held
     ``status`` word, sets ``ST_INVALID_TOUR`` there and the caller reads it."""
-    if (locs is None) == (distances is None):
-        raise ValueError("two_opt: give exactly one of locs and distances")
-    src = locs if locs is not None else distances
+    src, which = _pick_source("two_opt", locs, distances)
     nat.require_device(actions, src)
     if actions.dim() != 2:
         raise ValueError(f"two_opt: actions must be [B, N], got {tuple(actions.shape)}")
@@ -183,30 +224,18 @@ def two_opt(actions: Tensor, locs: Tensor = None, distances: Tensor = None,
     if n > nat.TWO_OPT_MAX_N:
         raise ValueError(f"two_opt: num_loc {n} exceeds the supported maximum "
                          f"{nat.TWO_OPT_MAX_N}")
-    want = (n, 2) if locs is not None else (n, n)
-    if src.dim() != 3 or tuple(src.shape[1:]) != want or src.shape[0] == 0 \
-            or b % src.shape[0] != 0:
-        raise ValueError(f"two_opt: {'locs' if locs is not None else 'distances'} of shape "
-                         f"{tuple(src.shape)} does not fit actions {tuple(actions.shape)}")
-    src = src.contiguous().float()
+    lb = src.shape[0] if src.dim() == 3 else 0
+    src, src_ptrs = _fit_source("two_opt", src, which, lb, n, b,
+                                f"actions {tuple(actions.shape)}")
     if actions.dtype != torch.int64:
         actions = actions.long()
-    out = torch.empty((b, n), dtype=torch.int64, device=actions.device)
-    sweeps = torch.empty(b, dtype=torch.int32, device=actions.device) if return_sweeps else None
-    if b == 0 or n == 0:
-        return (out, sweeps) if return_sweeps else out
-    own = status is None
-    if own:
-        status = nat.scratch_status(actions.device)
-    nat.call("co_tsp_two_opt", b, n, nat.ptr(src) if locs is not None else None,
-             nat.ptr(src) if locs is None else None, src.shape[0], nat.ptr(actions),
-             actions.stride(0), actions.stride(1), int(max_iterations), nat.ptr(out),
-             nat.ptr(sweeps), nat.ptr(status), nat.stream_of(actions))
-    if own:
-        bits = int(status.item())
-        nat.release_status(status, (bits,))
-        if bits & nat.ST_INVALID_TOUR:
-            raise AssertionError("Invalid tour")
+    out, sweeps = _search_outputs((b, n), torch.int64, actions.device, return_sweeps)
+    if b > 0 and n > 0:
+        _run_with_status(lambda st: nat.call(
+            "co_tsp_two_opt", b, n, *src_ptrs, lb, nat.ptr(actions), actions.stride(0),
+            actions.stride(1), int(max_iterations), nat.ptr(out), nat.ptr(sweeps), nat.ptr(st),
+            nat.stream_of(actions)),
+            status, actions.device, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])
     return (out, sweeps) if return_sweeps else out
 
 
@@ -225,9 +254,7 @@ def cvrp_local_search(actions: Tensor, demand: Tensor, locs: Tensor = None,
     does not visit every customer exactly once (or whose demands / capacity are not finite
     values in [0, 4096]) raises ``AssertionError("Invalid tour")`` -- or, with a caller-held
     ``status`` word, sets ``ST_INVALID_TOUR`` there and comes back unchanged."""
-    if (locs is None) == (distances is None):
-        raise ValueError("cvrp_local_search: give exactly one of locs and distances")
-    src = locs if locs is not None else distances
+    src, which = _pick_source("cvrp_local_search", locs, distances)
     nat.require_device(actions, demand, src, capacity)
     if actions.dim() != 2 or demand.dim() != 2:
         raise ValueError(f"cvrp_local_search: actions must be [B, T] and demand [LB, N], got "
@@ -239,35 +266,24 @@ def cvrp_local_search(actions: Tensor, demand: Tensor, locs: Tensor = None,
     if min(t, 2 * n) + 1 > nat.CVRP_LS_MAX_LEN:
         raise ValueError(f"cvrp_local_search: a giant tour of up to {min(t, 2 * n) + 1} "
                          f"positions exceeds the supported maximum {nat.CVRP_LS_MAX_LEN}")
-    want = (lb, n + 1, 2) if locs is not None else (lb, n + 1, n + 1)
-    if tuple(src.shape) != want or lb == 0 or b % lb != 0:
-        raise ValueError(f"cvrp_local_search: {'locs' if locs is not None else 'distances'} of "
-                         f"shape {tuple(src.shape)} does not fit actions {tuple(actions.shape)} "
-                         f"and demand {tuple(demand.shape)}")
+    src, src_ptrs = _fit_source("cvrp_local_search", src, which, lb, n + 1, b,
+                                f"actions {tuple(actions.shape)} and demand "
+                                f"{tuple(demand.shape)}")
     if capacity is not None:
         if capacity.numel() != lb:
             raise ValueError(f"cvrp_local_search: capacity of shape {tuple(capacity.shape)} "
                              f"does not fit demand {tuple(demand.shape)}")
         capacity = capacity.reshape(lb).contiguous().float()
-    src, demand = src.contiguous().float(), demand.contiguous().float()
+    demand = demand.contiguous().float()
     if actions.dtype != torch.int64:
         actions = actions.long()
-    out = torch.empty((b, t), dtype=torch.int64, device=actions.device)
-    sweeps = torch.empty(b, dtype=torch.int32, device=actions.device) if return_sweeps else None
-    if b == 0:
-        return (out, sweeps) if return_sweeps else out
-    own = status is None
-    if own:
-        status = nat.scratch_status(actions.device)
-    nat.call("co_cvrp_local_search", b, n, t, nat.ptr(src) if locs is not None else None,
-             nat.ptr(src) if locs is None else None, nat.ptr(demand), nat.ptr(capacity), lb,
-             nat.ptr(actions), actions.stride(0), actions.stride(1), int(max_iterations),
-             nat.ptr(out), nat.ptr(sweeps), nat.ptr(status), nat.stream_of(actions))
-    if own:
-        bits = int(status.item())
-        nat.release_status(status, (bits,))
-        if bits & nat.ST_INVALID_TOUR:
-            raise AssertionError("Invalid tour")
+    out, sweeps = _search_outputs((b, t), torch.int64, actions.device, return_sweeps)
+    if b > 0:
+        _run_with_status(lambda st: nat.call(
+            "co_cvrp_local_search", b, n, t, *src_ptrs, nat.ptr(demand), nat.ptr(capacity), lb,
+            nat.ptr(actions), actions.stride(0), actions.stride(1), int(max_iterations),
+            nat.ptr(out), nat.ptr(sweeps), nat.ptr(st), nat.stream_of(actions)),
+            status, actions.device, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])
     return (out, sweeps) if return_sweeps else out
 
 
@@ -289,9 +305,7 @@ def slap_local_search(assignment: Tensor, picklist: Tensor, locs: Tensor = None,
     ``IndexError`` -- or, with a caller-held ``status`` word, sets ``ST_INVALID_TOUR`` /
     ``ST_INDEX_RANGE`` there and comes back unchanged.  ``scheme`` (device only) forces the
     direct or the table evaluation scheme; the results do not depend on it."""
-    if (locs is None) == (distances is None):
-        raise ValueError("slap_local_search: give exactly one of locs and distances")
-    src = locs if locs is not None else distances
+    src, which = _pick_source("slap_local_search", locs, distances)
     nat.require_device(assignment, picklist, src)
     if assignment.dim() != 2 or picklist.dim() != 3:
         raise ValueError(f"slap_local_search: assignment must be [B, P] and picklist "
@@ -303,11 +317,9 @@ def slap_local_search(assignment: Tensor, picklist: Tensor, locs: Tensor = None,
     b, p = assignment.shape
     lb, o, k = picklist.shape
     l = src.shape[1] if src.dim() == 3 else -1
-    want = (lb, l, 2) if locs is not None else (lb, l, l)
-    if src.dim() != 3 or tuple(src.shape) != want or lb == 0 or b % lb != 0:
-        raise ValueError(f"slap_local_search: {'locs' if locs is not None else 'distances'} of "
-                         f"shape {tuple(src.shape)} does not fit assignment "
-                         f"{tuple(assignment.shape)} and picklist {tuple(picklist.shape)}")
+    src, src_ptrs = _fit_source("slap_local_search", src, which, lb, l, b,
+                                f"assignment {tuple(assignment.shape)} and picklist "
+                                f"{tuple(picklist.shape)}")
     if not 1 <= p <= nat.SLAP_LS_MAX_PRODUCTS:
         raise ValueError(f"slap_local_search: {p} products; the supported range is 1.."
                          f"{nat.SLAP_LS_MAX_PRODUCTS}")
@@ -317,7 +329,6 @@ def slap_local_search(assignment: Tensor, picklist: Tensor, locs: Tensor = None,
     if not 1 <= o * k <= 65536:
         raise ValueError(f"slap_local_search: {o} orders of {k} picks; 1..65536 picks are "
                          "supported")
-    src = src.contiguous().float()
     picklist = picklist.contiguous()
     if picklist.dtype != torch.int64:
         picklist = picklist.long()
@@ -327,8 +338,7 @@ def slap_local_search(assignment: Tensor, picklist: Tensor, locs: Tensor = None,
     if dtype == torch.int64:  # a slot beyond int32 must not wrap into range
         wild = (assignment < -1) | (assignment > l)
         assign = torch.where(wild, -1, assignment).to(torch.int32)
-    out = torch.empty((b, p), dtype=torch.int32, device=dev)
-    sweeps = torch.empty(b, dtype=torch.int32, device=dev) if return_sweeps else None
+    out, sweeps = _search_outputs((b, p), torch.int32, dev, return_sweeps)
     cost = torch.empty(b, dtype=torch.int64, device=dev) if return_cost else None
 
     def result():
@@ -340,29 +350,24 @@ def slap_local_search(assignment: Tensor, picklist: Tensor, locs: Tensor = None,
 
     if b == 0:
         return result()
-    own = status is None
-    if own:
-        status = nat.scratch_status(dev)
-    args = (b, l, p, o, k, nat.ptr(src) if locs is not None else None,
-            nat.ptr(src) if locs is None else None, lb, nat.ptr(picklist), nat.ptr(assign),
+    args = (b, l, p, o, k, *src_ptrs, lb, nat.ptr(picklist), nat.ptr(assign),
             int(max_iterations), nat.ptr(out), nat.ptr(sweeps), nat.ptr(cost))
-    if scheme == nat.SLAP_LS_AUTO:
-        nat.call("co_slap_local_search", *args, nat.ptr(status), nat.stream_of(assign))
-    else:
+
+    def launch(st):
+        if scheme == nat.SLAP_LS_AUTO:
+            nat.call("co_slap_local_search", *args, nat.ptr(st), nat.stream_of(assign))
+            return
         if dev.type == "cpu":
             raise ValueError("slap_local_search: the host build has one evaluation scheme")
         if scheme == nat.SLAP_LS_TABLE and not nat.slap_ls_table_fits(p, l):
             raise ValueError(f"slap_local_search: the table of {p} products x {l} slots does "
                              f"not fit the LDS budget of {nat.SLAP_LS_LDS_BYTES} bytes")
-        nat.call("co_slap_local_search_scheme", *args, int(scheme), nat.ptr(status),
+        nat.call("co_slap_local_search_scheme", *args, int(scheme), nat.ptr(st),
                  nat.stream_of(assign))
-    if own:
-        bits = int(status.item())
-        nat.release_status(status, (bits,))
-        if bits & nat.ST_INVALID_TOUR:
-            raise AssertionError("Invalid assignment")
-        if bits & nat.ST_INDEX_RANGE:
-            raise IndexError("index out of range in SLAP picklist")
+
+    _run_with_status(launch, status, dev, [
+        (nat.ST_INVALID_TOUR, AssertionError, "Invalid assignment"),
+        (nat.ST_INDEX_RANGE, IndexError, "index out of range in SLAP picklist")])
     return result()
 
 

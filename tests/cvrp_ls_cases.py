@@ -8,18 +8,11 @@ trailing zeros (and up to the widest row of its batch)."""
 import functools
 
 import numpy as np
-import torch
 
+from ls_cases_common import frozen, to_device, to_numpy
 from cvrp_ls_ref import dist_from_locs, local_search
 
 PAD = 3
-
-
-def _frozen(*arrays):
-    for a in arrays:
-        if isinstance(a, np.ndarray):
-            a.setflags(write=False)
-    return arrays
 
 
 def demands(rng, b, n, cap):
@@ -102,7 +95,7 @@ def uniform_case(b, n, cap=30, max_iterations=1000, lb=None):
     D = [dist_from_locs(l) for l in locs]
     tours = start_tours(D, demand, b, seed=b * 7 + n)
     ref, sweeps, tied = solve(D, demand, tours, max_iterations)
-    return _frozen(locs, demand, tours, ref, sweeps) + (tied,)
+    return frozen(locs, demand, tours, ref, sweeps) + (tied,)
 
 
 @functools.lru_cache(maxsize=None)
@@ -117,7 +110,7 @@ def grid_case():
     D = [dist_from_locs(pts)] * b
     tours = start_tours(D, demand, b, seed=6)
     ref, sweeps, tied = solve(D, demand, tours)
-    return _frozen(locs, demand, tours, ref, sweeps) + (tied,)
+    return frozen(locs, demand, tours, ref, sweeps) + (tied,)
 
 
 @functools.lru_cache(maxsize=None)
@@ -133,7 +126,7 @@ def int_matrix_case(b, n, symmetric, max_iterations=1000):
     demand = demands(rng, b, n, 30)
     tours = start_tours(D, demand, b, seed=n + 77)
     ref, sweeps, tied = solve(D, demand, tours, max_iterations)
-    return _frozen(D, demand, tours, ref, sweeps) + (tied,)
+    return frozen(D, demand, tours, ref, sweeps) + (tied,)
 
 
 _LINE = np.array([(0, 0), (1, 0), (2, 0)], dtype=np.float32)
@@ -156,10 +149,9 @@ KNOWN = [
 def run(fn, tours, demand, locs=None, distances=None, capacity=None, device="cpu", **kw):
     """Call ``ops.cvrp_local_search`` on numpy inputs moved to ``device``; numpy
     (rows, sweeps)."""
-    def dev(a, dt):  # copies: the cases are read-only
-        return None if a is None else torch.from_numpy(np.array(a, dtype=dt)).to(device)
+    def dev(a, dt):
+        return to_device(a, dt, device)
 
-    out, sw = fn(dev(tours, np.int64), dev(demand, np.float32), locs=dev(locs, np.float32),
-                 distances=dev(distances, np.float32), capacity=dev(capacity, np.float32),
-                 return_sweeps=True, **kw)
-    return out.cpu().numpy(), sw.cpu().numpy()
+    return to_numpy(fn(dev(tours, np.int64), dev(demand, np.float32),
+                       locs=dev(locs, np.float32), distances=dev(distances, np.float32),
+                       capacity=dev(capacity, np.float32), return_sweeps=True, **kw))

@@ -1,5 +1,5 @@
 // Sanitizer driver for the host co_cvrp_local_search (csrc/host/co_env_host.cpp), compiled
-// together with it under -fsanitize=address,undefined by tests/test_host_cvrp_ls_asan.py:
+// together with it under -fsanitize=address,undefined by tests/test_host_asan.py:
 // exactly-sized heap buffers (any out-of-bounds index is an ASan report), both distance
 // sources, row-major and step-major actions, a multistart instance batch, N in
 // {1, 2, 3, 21, 65}, explicit and default capacity, invalid rows, max_iterations = 0 and
@@ -13,16 +13,9 @@
 #include <vector>
 
 #include "../../include/co_env.h"
+#include "check.h"
 
 static std::mt19937_64 rng(2025);
-
-#define CHECK(x)                                                              \
-  do {                                                                        \
-    if (!(x)) {                                                               \
-      std::fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #x);     \
-      return 1;                                                               \
-    }                                                                         \
-  } while (0)
 
 static double route_len(const float* D, int64_t V, const int64_t* t, int64_t T) {
   double s = 0;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/co_env.h"
+#include "check.h"
 
 static std::mt19937_64 rng(12345);
 static int64_t ri(int64_t lo, int64_t hi) {  // [lo, hi]
@@ -19,22 +20,13 @@ static int64_t ri(int64_t lo, int64_t hi) {  // [lo, hi]
 }
 static float rf() { return std::uniform_real_distribution<float>(0.f, 1.f)(rng); }
 
-#define CHECK(x)                                                    \
-  do {                                                              \
-    int rc_ = (x);                                                  \
-    if (rc_ != CO_OK) {                                             \
-      std::fprintf(stderr, "%s:%d: %s -> %d\n", __FILE__, __LINE__, #x, rc_); \
-      return 1;                                                     \
-    }                                                               \
-  } while (0)
-
 static int tsp(int64_t B, int64_t N) {
   std::vector<uint8_t> m0(B * N), m1(B * N);
   std::vector<int64_t> first(B), cur(B), i0(B), i1(B), act(B), f2(B);
   std::vector<float> rw(B);
   std::vector<uint8_t> done(B), srw(B);
   int32_t st = 0, flag = 0;
-  CHECK(co_tsp_reset(B, N, m0.data(), first.data(), cur.data(), i0.data(), rw.data(), nullptr));
+  CHECK_OK(co_tsp_reset(B, N, m0.data(), first.data(), cur.data(), i0.data(), rw.data(), nullptr));
   std::vector<int64_t> acts(B * N);  // row-major [B, N]
   for (int64_t b = 0; b < B; ++b) {
     std::vector<int64_t> p(N);
@@ -46,9 +38,9 @@ static int tsp(int64_t B, int64_t N) {
     for (int64_t b = 0; b < B; ++b) act[b] = acts[b * N + t];
     if (t == 1 && B > 0) act[0] = N + 7;   // out of range
     if (t == 2 && B > 1) act[1] = -3;
-    CHECK(co_any_eq_i64(i0.data(), B, 0, &flag, nullptr));
+    CHECK_OK(co_any_eq_i64(i0.data(), B, 0, &flag, nullptr));
     const bool inplace = t % 2;
-    CHECK(co_tsp_step(B, N, act.data(), m0.data(), inplace ? m0.data() : m1.data(), i0.data(),
+    CHECK_OK(co_tsp_step(B, N, act.data(), m0.data(), inplace ? m0.data() : m1.data(), i0.data(),
                       i1.data(), first.data(), f2.data(), cur.data(), done.data(), srw.data(),
                       2, &flag, &st, nullptr));
     if (!inplace) m0.swap(m1);
@@ -63,10 +55,10 @@ static int tsp(int64_t B, int64_t N) {
     for (int64_t t = 0; t < N; ++t) sm[t * B + b] = acts[b * N + t];
   if (B > 2) acts[2 * N + 1] = -1;
   const int64_t LB = B > 0 ? B : 1;
-  CHECK(co_tsp_reward(B, N, N, locs.data(), LB, acts.data(), N, 1, 1, rw.data(), &st, nullptr));
-  CHECK(co_tsp_reward(B, N, N, locs.data(), LB, sm.data(), 1, B, 0, rw.data(), &st, nullptr));
+  CHECK_OK(co_tsp_reward(B, N, N, locs.data(), LB, acts.data(), N, 1, 1, rw.data(), &st, nullptr));
+  CHECK_OK(co_tsp_reward(B, N, N, locs.data(), LB, sm.data(), 1, B, 0, rw.data(), &st, nullptr));
   if (B % 2 == 0 && B > 0)
-    CHECK(co_tsp_reward(B, N, N, locs.data(), B / 2, sm.data(), 1, B, 1, rw.data(), &st,
+    CHECK_OK(co_tsp_reward(B, N, N, locs.data(), B / 2, sm.data(), 1, B, 1, rw.data(), &st,
                         nullptr));
   return 0;
 }
@@ -81,7 +73,7 @@ static int cvrp(int64_t B, int64_t N) {
   std::vector<int64_t> cur(B), act(B);
   std::vector<uint8_t> v0(B * NC), v1(B * NC), mask(B * NC), done(B), srw(B);
   int32_t st = 0, nd = 0;
-  CHECK(co_cvrp_reset(B, N, depot.data(), lin.data(), dem.data(), 1.0f, lout.data(), cur.data(),
+  CHECK_OK(co_cvrp_reset(B, N, depot.data(), lin.data(), dem.data(), 1.0f, lout.data(), cur.data(),
                       u0.data(), vc.data(), v0.data(), mask.data(), nullptr));
   const int64_t T = 3 * N;
   std::vector<int64_t> acts(B * T);
@@ -93,20 +85,20 @@ static int cvrp(int64_t B, int64_t N) {
       acts[b * T + t] = a;
     }
     const bool inplace = t % 3 == 0;
-    CHECK(co_cvrp_step(B, N, act.data(), dem.data(), u0.data(), u1.data(), vc.data(), v0.data(),
+    CHECK_OK(co_cvrp_step(B, N, act.data(), dem.data(), u0.data(), u1.data(), vc.data(), v0.data(),
                        inplace ? v0.data() : v1.data(), cur.data(), done.data(), srw.data(),
                        mask.data(), &st, &nd, nullptr));
     if (!inplace) v0.swap(v1);
     u0.swap(u1);
-    CHECK(co_cvrp_action_mask(B, N, dem.data(), u0.data(), vc.data(), v0.data(), cur.data(),
+    CHECK_OK(co_cvrp_action_mask(B, N, dem.data(), u0.data(), vc.data(), v0.data(), cur.data(),
                               mask.data(), nullptr));
   }
   std::vector<int64_t> sm(T * B);
   for (int64_t b = 0; b < B; ++b)
     for (int64_t t = 0; t < T; ++t) sm[t * B + b] = acts[b * T + t];
-  CHECK(co_cvrp_reward(B, N, T, lout.data(), acts.data(), T, 1, dem.data(), vc.data(), 1,
+  CHECK_OK(co_cvrp_reward(B, N, T, lout.data(), acts.data(), T, 1, dem.data(), vc.data(), 1,
                        rw.data(), &st, nullptr));
-  CHECK(co_cvrp_reward(B, N, T, lout.data(), sm.data(), 1, B, dem.data(), vc.data(), 0, rw.data(),
+  CHECK_OK(co_cvrp_reward(B, N, T, lout.data(), sm.data(), 1, B, dem.data(), vc.data(), 0, rw.data(),
                        &st, nullptr));
   return 0;
 }
@@ -118,12 +110,12 @@ static int slap(int64_t B, int64_t L, int64_t P, int64_t O, int64_t K) {
   std::vector<int64_t> i0(B), i1(B), act(B), pick(B * O * K);
   std::vector<int32_t> a0(B * P, -1), a1(B * P);
   int32_t st = 0;
-  CHECK(co_slap_reset(B, L, P, m0.data(), tc.data(), i0.data(), rw.data(), ratio.data(), dn.data(), tm.data(), nullptr));
+  CHECK_OK(co_slap_reset(B, L, P, m0.data(), tc.data(), i0.data(), rw.data(), ratio.data(), dn.data(), tm.data(), nullptr));
   for (int64_t t = 0; t < P; ++t) {
     for (int64_t b = 0; b < B; ++b) act[b] = ri(-L - 2, L + 2);  // wraps and out of range
     if (t == 1 && B > 0) tc[0 * P + t] = (float)(P + 3);        // product out of range
     const bool inplace = t % 2;
-    CHECK(co_slap_step(B, L, P, act.data(), tc.data() + t, P, a0.data(),
+    CHECK_OK(co_slap_step(B, L, P, act.data(), tc.data() + t, P, a0.data(),
                        inplace ? a0.data() : a1.data(), m0.data(), inplace ? m0.data() : m1.data(),
                        i0.data(), i1.data(), done.data(), srw.data(), &st, nullptr));
     if (!inplace) {
@@ -133,7 +125,7 @@ static int slap(int64_t B, int64_t L, int64_t P, int64_t O, int64_t K) {
     i0.swap(i1);
   }
   for (auto& p : pick) p = ri(-P - 2, P + 1);
-  CHECK(co_slap_reward(B, L, P, O, K, a0.data(), pick.data(), locs.data(), rw.data(), &st,
+  CHECK_OK(co_slap_reward(B, L, P, O, K, a0.data(), pick.data(), locs.data(), rw.data(), &st,
                        nullptr));
   return 0;
 }
@@ -143,7 +135,7 @@ static int gather(int64_t outer, int64_t len, int64_t inner, int64_t m) {
   std::vector<int64_t> idx(outer * m);
   for (auto& j : idx) j = ri(-2, len + 1);
   int32_t st = 0;
-  CHECK(co_gather_by_index(src.data(), outer, len, inner * 4, len * inner * 4, inner * 4,
+  CHECK_OK(co_gather_by_index(src.data(), outer, len, inner * 4, len * inner * 4, inner * 4,
                            idx.data(), m, m, 1, dst.data(), &st, nullptr));
   return 0;
 }
@@ -165,10 +157,10 @@ static int decode(int64_t B, int64_t N) {
   for (int mode = 0; mode < 3; ++mode)
     for (float clip : {0.f, 10.f})
       for (float temp : {1.f, 0.5f}) {
-        CHECK(co_decode_step(B, N, lg.data(), N, mask.data(), clip, temp, mode, ain.data(),
+        CHECK_OK(co_decode_step(B, N, lg.data(), N, mask.data(), clip, temp, mode, ain.data(),
                              aout.data(), lp.data(), full.data(), 99, (uint64_t)mode, &st,
                              nullptr));
-        CHECK(co_decode_step(B, N, lg.data(), N, nullptr, clip, temp, mode | CO_DECODE_FAST,
+        CHECK_OK(co_decode_step(B, N, lg.data(), N, nullptr, clip, temp, mode | CO_DECODE_FAST,
                              ain.data(), aout.data(), lp.data(), nullptr, 7, 1, &st, nullptr));
       }
   return 0;

@@ -1,5 +1,5 @@
 // Sanitizer driver for the host co_slap_local_search (csrc/host/co_env_host.cpp), compiled
-// together with it under -fsanitize=address,undefined by tests/test_host_slap_ls_asan.py:
+// together with it under -fsanitize=address,undefined by tests/test_host_asan.py:
 // exactly-sized heap buffers (any out-of-bounds index is an ASan report), both distance
 // sources, a multistart instance batch, (P, L) in {(1, 2), (2, 3), (5, 8), (20, 100),
 // (31, 32), (64, 130)}, rows that fail each part of the check, max_iterations = 0 and the
@@ -14,16 +14,9 @@
 #include <vector>
 
 #include "../../include/co_env.h"
+#include "check.h"
 
 static std::mt19937_64 rng(2026);
-
-#define CHECK(x)                                                              \
-  do {                                                                        \
-    if (!(x)) {                                                               \
-      std::fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #x);     \
-      return 1;                                                               \
-    }                                                                         \
-  } while (0)
 
 static int64_t objective(const float* D, int64_t L, const int64_t* pl, int64_t O, int64_t K,
                          const int32_t* s) {

@@ -1,5 +1,5 @@
 // Sanitizer driver for the host co_tsp_two_opt (csrc/host/co_env_host.cpp), compiled
-// together with it under -fsanitize=address,undefined by tests/test_host_two_opt_asan.py:
+// together with it under -fsanitize=address,undefined by tests/test_host_asan.py:
 // exactly-sized heap buffers (any out-of-bounds index is an ASan report), both distance
 // sources, row-major and step-major actions, a multistart coordinate batch, N in
 // {1, 3, 4, 65}, an invalid row, max_iterations = 0 and the argument errors.  Each result
@@ -12,16 +12,9 @@
 #include <vector>
 
 #include "../../include/co_env.h"
+#include "check.h"
 
 static std::mt19937_64 rng(2024);
-
-#define CHECK(x)                                                              \
-  do {                                                                        \
-    if (!(x)) {                                                               \
-      std::fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #x);     \
-      return 1;                                                               \
-    }                                                                         \
-  } while (0)
 
 static double tour_len(const std::vector<float>& D, int64_t n, const int64_t* t) {
   double s = 0;

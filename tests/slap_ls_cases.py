@@ -10,6 +10,7 @@ import functools
 import numpy as np
 import torch
 
+from ls_cases_common import frozen, to_device, to_numpy
 from slap_ls_ref import dist_from_locs, local_search
 from rl4co_slap_amd import TensorDict
 from rl4co_slap_amd._native import ST_INDEX_RANGE, ST_INVALID_TOUR
@@ -22,13 +23,6 @@ SHAPES = [(37, 1, 2, 1, 1, 1000), (37, 2, 3, 2, 2, 1000), (64, 5, 8, 4, 3, 1000)
 
 # (P, L) on either side of the device's table / direct cut (CO_SLAP_LS_TABLE_FITS)
 CUT_SHAPES = [(32, 239), (32, 240), (50, 147), (50, 148)]
-
-
-def _frozen(*arrays):
-    for a in arrays:
-        if isinstance(a, np.ndarray):
-            a.setflags(write=False)
-    return arrays
 
 
 def grid_locs(n_aisles=10, n_locs=10, inter_aisle=2.4, inter_loc=1.0):
@@ -87,7 +81,7 @@ def coords_case(b, p, L, o, k, max_iterations=1000, lb=None, grid=False):
     D = [dist_from_locs(l) for l in locs]
     rows = start_rows(rng, D, b, p)
     ref, sweeps, cost, tied = solve(D, picklist, rows, max_iterations, locs)
-    return _frozen(locs, picklist, rows, ref, sweeps, cost) + (tied,)
+    return frozen(locs, picklist, rows, ref, sweeps, cost) + (tied,)
 
 
 @functools.lru_cache(maxsize=None)
@@ -103,7 +97,7 @@ def int_matrix_case(b, symmetric, p=12, L=14, o=10, k=4, max_iterations=1000):
     picklist = rng.integers(0, p, size=(b, o, k)).astype(np.int64)
     rows = start_rows(rng, D, b, p)
     ref, sweeps, cost, tied = solve(D, picklist, rows, max_iterations)
-    return _frozen(D, picklist, rows, ref, sweeps, cost) + (tied,)
+    return frozen(D, picklist, rows, ref, sweeps, cost) + (tied,)
 
 
 @functools.lru_cache(maxsize=None)
@@ -116,7 +110,7 @@ def matrix_case(b, p, L, o, k, max_iterations=1000):
     picklist = rng.integers(0, p, size=(b, o, k)).astype(np.int64)
     rows = start_rows(rng, D, b, p)
     ref, sweeps, cost, tied = solve(D, picklist, rows, max_iterations)
-    return _frozen(D, picklist, rows, ref, sweeps, cost) + (tied,)
+    return frozen(D, picklist, rows, ref, sweeps, cost) + (tied,)
 
 
 _LINE4 = np.array([(0, 0), (1, 0), (2, 0), (3, 0)], dtype=np.float32)
@@ -144,13 +138,12 @@ KNOWN = [
 def run(fn, rows, picklist, locs=None, distances=None, device="cpu", dtype=np.int32, **kw):
     """Call ``ops.slap_local_search`` on numpy inputs moved to ``device``; numpy
     (rows, sweeps, cost)."""
-    def dev(a, dt):  # copies: the cases are read-only
-        return None if a is None else torch.from_numpy(np.array(a, dtype=dt)).to(device)
+    def dev(a, dt):
+        return to_device(a, dt, device)
 
-    out, sw, cost = fn(dev(rows, dtype), dev(picklist, np.int64), locs=dev(locs, np.float32),
+    return to_numpy(fn(dev(rows, dtype), dev(picklist, np.int64), locs=dev(locs, np.float32),
                        distances=dev(distances, np.float32), return_sweeps=True,
-                       return_cost=True, **kw)
-    return out.cpu().numpy(), sw.cpu().numpy(), cost.cpu().numpy()
+                       return_cost=True, **kw))
 
 
 def slap_td(locs, pl, rows, dev="cpu", dist=None):

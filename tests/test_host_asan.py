@@ -1,8 +1,10 @@
 """The host build's indexing under AddressSanitizer + UndefinedBehaviorSanitizer
-(sanitizers on host code): tests/host_asan/driver.cpp is compiled
-together with csrc/host/co_env_host.cpp by g++ with -fsanitize=address,undefined
-(-fno-sanitize-recover: any report fails the run) and executed as its own process.  CPU
-only; skipped where g++ or the sanitizer runtimes are absent."""
+(sanitizers on host code): each driver under tests/host_asan/ is
+compiled together with csrc/host/co_env_host.cpp by g++ with -fsanitize=address,undefined
+(-fno-sanitize-recover: any report fails the run) and executed as its own process --
+driver.cpp for the env / decode entry points, two_opt_driver.cpp, cvrp_ls_driver.cpp and
+slap_ls_driver.cpp for the three local searches.  CPU only; skipped where g++ or the
+sanitizer runtimes are absent."""
 import os
 import shutil
 import subprocess
@@ -12,14 +14,16 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_host_build_is_sanitizer_clean(tmp_path):
+@pytest.mark.parametrize("driver", ["driver", "two_opt_driver", "cvrp_ls_driver",
+                                    "slap_ls_driver"])
+def test_host_build_is_sanitizer_clean(tmp_path, driver):
     cxx = shutil.which("g++")
     if cxx is None:
         pytest.skip("g++ not available")
-    exe = tmp_path / "host_asan"
+    exe = tmp_path / (driver + "_asan")
     cmd = [cxx, "-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer", "-ffp-contract=off",
            "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           os.path.join(ROOT, "tests", "host_asan", "driver.cpp"),
+           os.path.join(ROOT, "tests", "host_asan", driver + ".cpp"),
            os.path.join(ROOT, "rl4co_slap_amd", "csrc", "host", "co_env_host.cpp"),
            "-o", str(exe)]
     b = subprocess.run(cmd, capture_output=True, text=True)

@@ -4,8 +4,8 @@ tests/two_opt_ref.py once per session and handed out read-only."""
 import functools
 
 import numpy as np
-import torch
 
+from ls_cases_common import frozen, to_device, to_numpy
 from two_opt_ref import dist_from_locs, two_opt
 
 E23 = 2.0 ** -23
@@ -32,13 +32,6 @@ def solve(D, tours, max_iterations=1000):
     return (np.stack(out).reshape(len(tours), -1), np.asarray(sweeps, dtype=np.int32), tied)
 
 
-def _frozen(*arrays):
-    for a in arrays:
-        if isinstance(a, np.ndarray):
-            a.setflags(write=False)
-    return arrays
-
-
 @functools.lru_cache(maxsize=None)
 def uniform_case(b, n, max_iterations=1000, lb=None):
     """Random uniform coordinates [lb or b, n, 2], random tours [b, n] and the restatement's
@@ -47,7 +40,7 @@ def uniform_case(b, n, max_iterations=1000, lb=None):
     tours = perms(b, n, seed=b * 7 + n)
     D = [dist_from_locs(l) for l in locs]
     ref, sweeps, _ = solve(D, tours, max_iterations)
-    return _frozen(locs, tours, ref, sweeps)
+    return frozen(locs, tours, ref, sweeps)
 
 
 @functools.lru_cache(maxsize=None)
@@ -57,7 +50,7 @@ def grid_case():
     locs = np.repeat(pts[None], 32, 0)
     tours = perms(32, 16, seed=5)
     ref, sweeps, tied = solve([dist_from_locs(pts)], tours)
-    return _frozen(locs, tours, ref, sweeps) + (tied,)
+    return frozen(locs, tours, ref, sweeps) + (tied,)
 
 
 @functools.lru_cache(maxsize=None)
@@ -70,7 +63,7 @@ def int_matrix_case(b, n, symmetric, max_iterations=1000):
         D = np.triu(D, 1) + np.transpose(np.triu(D, 1), (0, 2, 1)) + np.eye(n, dtype=np.float32)
     tours = perms(b, n, seed=n + 77)
     ref, sweeps, tied = solve(D, tours, max_iterations)
-    return _frozen(np.ascontiguousarray(D), tours, ref, sweeps) + (tied,)
+    return frozen(np.ascontiguousarray(D), tours, ref, sweeps) + (tied,)
 
 
 def _ones4(eps_units):
@@ -92,9 +85,7 @@ KNOWN = [
 
 def run(two_opt_fn, tours, locs=None, distances=None, device="cpu", **kw):
     """Call ``ops.two_opt`` on numpy inputs moved to ``device``; numpy (tours, sweeps)."""
-    t = torch.from_numpy(np.array(tours, dtype=np.int64)).to(device)  # copies: cases are read-only
-    src = torch.from_numpy(np.array(locs if locs is not None else distances,
-                                    dtype=np.float32)).to(device)
-    out, sw = two_opt_fn(t, locs=src if locs is not None else None,
-                         distances=src if locs is None else None, return_sweeps=True, **kw)
-    return out.cpu().numpy(), sw.cpu().numpy()
+    return to_numpy(two_opt_fn(to_device(tours, np.int64, device),
+                               locs=to_device(locs, np.float32, device),
+                               distances=to_device(distances, np.float32, device),
+                               return_sweeps=True, **kw))

@@ -10,9 +10,7 @@ with the device's.
 Usage: python tools/bench_cvrp_ls.py [--quick] -> one JSON line."""
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,8 +20,7 @@ import torch  # noqa: E402
 from rl4co_slap_amd import _native as nat  # noqa: E402
 from rl4co_slap_amd.envs.cvrp import CAPACITIES  # noqa: E402
 from rl4co_slap_amd.utils.ops import cvrp_local_search, get_distance_matrix  # noqa: E402
-
-HOST_ROWS, HOST_THREADS = 256, 1
+from ls_bench import HOST_THREADS, host_leg, same_rows, timed  # noqa: E402
 
 
 def split_tours(demand, gen):
@@ -80,26 +77,14 @@ def evaluations(tours, sweeps, n):
 
 def measure(locs, demand, tours, dev):
     n = demand.shape[1]
-    out, sweeps = cvrp_local_search(tours, demand, locs=locs, return_sweeps=True)  # warm-up
-    torch.cuda.synchronize(dev)
-    ms = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out, sweeps = cvrp_local_search(tours, demand, locs=locs, return_sweeps=True)
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    ms = statistics.median(ms)
+    ms, (out, sweeps) = timed(
+        lambda: cvrp_local_search(tours, demand, locs=locs, return_sweeps=True), dev)
     total = int(sweeps.sum().item())
     evals, m_mean = evaluations(tours, sweeps, n)
-    hl, hd, ht = locs[:HOST_ROWS].cpu(), demand[:HOST_ROWS].cpu(), tours[:HOST_ROWS].cpu()
-    t0 = time.perf_counter()
-    hout, hsw = cvrp_local_search(ht, hd, locs=hl, return_sweeps=True)
-    host_ms = (time.perf_counter() - t0) * 1e3
+    (ht, hd, hl), host_ms, (hout, hsw) = host_leg(
+        lambda t, d, l: cvrp_local_search(t, d, locs=l, return_sweeps=True), tours, demand, locs)
     host_evals, _ = evaluations(ht, hsw, n)
-    same = bool(torch.equal(hout, out[:HOST_ROWS].cpu())
-                and torch.equal(hsw, sweeps[:HOST_ROWS].cpu()))
+    same = same_rows((hout, hsw), (out, sweeps))
     return {"ms_per_call_events": round(ms, 4), "steps": tours.shape[1],
             "tour_positions_mean": round(m_mean, 1), "sweeps_total": total,
             "sweeps_mean": round(total / tours.shape[0], 2),

@@ -14,9 +14,7 @@ shape beyond it, two of them on an explicit matrix as well.
 Usage: python tools/bench_slap_ls.py [--quick] -> one JSON line."""
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,23 +26,9 @@ from rl4co_slap_amd import _native as nat  # noqa: E402
 from rl4co_slap_amd.envs import SLAPEnv  # noqa: E402
 from rl4co_slap_amd.envs.slap import SLAPGenerator  # noqa: E402
 from rl4co_slap_amd.utils.ops import get_distance_matrix, slap_local_search  # noqa: E402
+from ls_bench import HOST_THREADS, host_leg, same_rows, timed  # noqa: E402
 
-HOST_ROWS, HOST_THREADS = 256, 1
 SCHEMES = {"table": nat.SLAP_LS_TABLE, "direct": nat.SLAP_LS_DIRECT}
-
-
-def timed(fn, dev):
-    fn()  # warm-up
-    torch.cuda.synchronize(dev)
-    ms = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        res = fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return statistics.median(ms), res
 
 
 def measure(assign, picklist, dev, schemes, locs=None, distances=None, host=True):
@@ -78,19 +62,15 @@ def measure(assign, picklist, dev, schemes, locs=None, distances=None, host=True
             td = TensorDict({"assignment": a, "picklist": picklist, "locs": locs}, [b])
             res[key] = round(float(env.get_reward(td, None).mean().item()), 3)
     if host:
-        h = [None if x is None else x[:HOST_ROWS].cpu() for x in (assign, picklist, locs, distances)]
-        t0 = time.perf_counter()
-        hout, hsw, hcost = slap_local_search(h[0], h[1], locs=h[2], distances=h[3],
-                                             return_sweeps=True, return_cost=True)
-        host_ms = (time.perf_counter() - t0) * 1e3
+        h, host_ms, (hout, hsw, hcost) = host_leg(
+            lambda a, pl, xy, d: slap_local_search(a, pl, locs=xy, distances=d, return_sweeps=True,
+                                                   return_cost=True),
+            assign, picklist, locs, distances)
         res.update({"host_rows": h[0].shape[0], "host_threads": HOST_THREADS,
                     "host_ms_wall": round(host_ms, 2),
                     "host_candidate_evals_per_s": round(
                         int(hsw.sum().item()) * per_sweep / (host_ms * 1e-3), 1),
-                    "host_equals_device": bool(
-                        torch.equal(hout, out[:HOST_ROWS].cpu())
-                        and torch.equal(hsw, sweeps[:HOST_ROWS].cpu())
-                        and torch.equal(hcost, cost[:HOST_ROWS].cpu()))})
+                    "host_equals_device": same_rows((hout, hsw, hcost), (out, sweeps, cost))})
     return res
 
 

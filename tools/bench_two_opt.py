@@ -7,9 +7,7 @@ run on the first 256 rows (wall clock, one thread: the host library is single-th
 Usage: python tools/bench_two_opt.py [--quick] -> one JSON line."""
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,8 +16,7 @@ import torch  # noqa: E402
 
 from rl4co_slap_amd import _native as nat  # noqa: E402
 from rl4co_slap_amd.utils.ops import get_distance_matrix, two_opt  # noqa: E402
-
-HOST_ROWS, HOST_THREADS = 256, 1
+from ls_bench import HOST_THREADS, host_leg, same_rows, timed  # noqa: E402
 
 
 def nearest_neighbour_tours(locs):
@@ -40,25 +37,13 @@ def nearest_neighbour_tours(locs):
 
 def measure(locs, tours, dev):
     n = tours.shape[1]
-    out, sweeps = two_opt(tours, locs=locs, return_sweeps=True)  # warm-up
-    torch.cuda.synchronize(dev)
-    ms = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out, sweeps = two_opt(tours, locs=locs, return_sweeps=True)
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    ms = statistics.median(ms)
+    ms, (out, sweeps) = timed(lambda: two_opt(tours, locs=locs, return_sweeps=True), dev)
     total = int(sweeps.sum().item())
     evals = total * (n - 1) * (n - 2) // 2
-    hl, ht = locs[:HOST_ROWS].cpu(), tours[:HOST_ROWS].cpu()
-    t0 = time.perf_counter()
-    hout, hsw = two_opt(ht, locs=hl, return_sweeps=True)
-    host_ms = (time.perf_counter() - t0) * 1e3
+    (ht, hl), host_ms, (hout, hsw) = host_leg(
+        lambda t, l: two_opt(t, locs=l, return_sweeps=True), tours, locs)
     host_evals = int(hsw.sum().item()) * (n - 1) * (n - 2) // 2
-    same = bool(torch.equal(hout, out[:HOST_ROWS].cpu()) and torch.equal(hsw, sweeps[:HOST_ROWS].cpu()))
+    same = same_rows((hout, hsw), (out, sweeps))
     return {"ms_per_call_events": round(ms, 4), "sweeps_total": total,
             "sweeps_mean": round(total / tours.shape[0], 2), "sweeps_max": int(sweeps.max().item()),
             "candidate_evals_per_s": round(evals / (ms * 1e-3), 1),
