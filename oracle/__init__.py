@@ -34,18 +34,24 @@ The SLAP per-batch Python loop (``slap/env.py:61-62``), the SLAP per-order loop
 (``envs/common/base.py:186-187`` + ``tsp/env.py:158-159``) are kept on purpose:
 this is also the CPU baseline that ``bench.py`` times.
 
+* ``reference.py`` / ``record_reference.py``  load the reference's own modules
+                   through stand-ins for their missing dependencies, in a process
+                   of its own, and record what its functions return into
+                   ``tests/golden/ref_<group>.npz``.
+
 Parity status
 -------------
-PARITY UNPINNED BY REFERENCE-HELD VECTORS.  The reference's own tests assert
-shapes only (``tests/test_envs.py:56-59``, ``tests/test_policy.py:25-51``) and
-hold no golden values; importing/running the reference in this pipeline was
-denied.  The oracle is instead pinned by
-(1) the reference's shape tests re-stated in ``tests/test_oracle.py``,
-(2) hand-derived known-answer tests written from the cited source lines
+PINNED TO RECORDINGS OF THE REFERENCE'S OWN CODE.  The reference's own tests
+assert shapes only (``tests/test_envs.py:56-59``, ``tests/test_policy.py:25-51``)
+and hold no golden values, and the oracle was written from the source text
+(SURVEY.md section 8c).  ``tests/test_reference_recordings.py`` now compares it,
+case by case, with what the reference's functions returned
+(``python -m oracle.record_reference``); the deliberate differences are listed
+in DESIGN.md section 2.  It is also pinned by
+(1) hand-derived known-answer tests written from the cited source lines
     (``tests/test_oracle_kat.py``), and
-(3) the reference's one value-level invariant test, the batchify round trip
+(2) the reference's one value-level invariant test, the batchify round trip
     (``tests/test_utils.py:98-116`` of the reference).
-Golden fixtures under ``tests/golden/`` are produced by this oracle
-(``tests/golden/make_golden.py``) and are therefore self-consistent, not
-reference-pinned.
+The other golden fixtures under ``tests/golden/`` are produced by this oracle
+(``tests/golden/make_golden.py``) at the benchmark's shapes.
 """

@@ -52,6 +52,11 @@ def get_tour_length(ordered_locs):
     return get_distance(nxt, ordered_locs).sum(-1)
 
 
+def get_distance_matrix(locs):
+    """``ops.py:104-111``."""
+    return (locs[..., :, None, :] - locs[..., None, :, :]).norm(p=2, dim=-1)
+
+
 def get_num_starts(td, env_name=None):
     """``ops.py:126-136`` (only the branches reachable by tsp/cvrp/slap matter here)."""
     n = td["action_mask"].shape[-1]

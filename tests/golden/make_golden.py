@@ -1,7 +1,10 @@
 """Golden fixtures for the hot path, produced by the oracle -- the CPU
-restatement of the reference's env / decode / POMO code (``oracle/``).  The reference
-itself may not be executed here, so these vectors pin the HIP path and
-guard the oracle against drift; they are data only (inputs and expected outputs).
+restatement of the reference's env / decode / POMO code (``oracle/``).  These vectors pin
+the HIP path at the benchmark's shapes and guard the oracle against drift; they are data
+only (inputs and expected outputs).  What the reference's own code computes is recorded
+separately, at small shapes, in ``ref_<group>.npz`` (``python -m oracle.record_reference``,
+which does run the reference's functions; tests/test_reference_recordings.py holds the
+oracle to them), so the oracle these fixtures come from is itself pinned to the reference.
 
     python tests/golden/make_golden.py          # rewrite the .npz files
     build_all()                                  # the same dicts, for the tests
