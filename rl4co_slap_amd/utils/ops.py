@@ -73,7 +73,9 @@ def gather_by_index(src: Tensor, idx: Tensor, dim: int = 1, squeeze: bool = True
     the trailing dims, which must be contiguous); ``idx`` must have shape
     ``src.shape[:dim] + (M,)`` (trailing singleton dims allowed), which covers every
     call site on the hot path (rewards, CVRP demand, context embeddings, logprob
-    gather, POMO best actions).
+    gather, POMO best actions).  An empty batch, index or trailing block gives the empty
+    tensor ``torch.gather`` gives (no launch); an empty ``src`` under a non-empty index is
+    an out-of-range index like any other.
     """
     nat.require_device(src, idx)
     dim = dim % src.dim()
@@ -91,31 +93,37 @@ def gather_by_index(src: Tensor, idx: Tensor, dim: int = 1, squeeze: bool = True
     inner = 1
     for t in trail:
         inner *= t
+    m = idx.shape[-1]
+    out = torch.empty((*lead, m, *trail), dtype=src.dtype, device=src.device)
+    if out.numel() == 0:  # an empty batch / index / trailing block: nothing to gather
+        return out.squeeze(dim) if squeeze and m == 1 else out
+    empty_src = src.shape[dim] == 0  # every index is out of range: the kernel reports it
     # the trailing block must be dense; leading dims must flatten to one stride
-    if inner > 1 and not src[(0,) * (dim + 1)].is_contiguous():
+    if inner > 1 and not empty_src and not src[(0,) * (dim + 1)].is_contiguous():
         src = src.contiguous()
     outer = 1
     for t in lead:
         outer *= t
     if dim > 0:
         try:
-            flat = src.view(outer, src.shape[dim], *trail) if outer > 0 else src
+            flat = src.view(outer, src.shape[dim], *trail)
         except RuntimeError:
             src = src.contiguous()
             flat = src.view(outer, src.shape[dim], *trail)
     else:
         flat = src.unsqueeze(0)
         outer = 1
-    idx2 = idx.reshape(outer, idx.shape[-1])
-    m = idx2.shape[1]
+    idx2 = idx.reshape(outer, m)
     es = src.element_size()
-    out = torch.empty((*lead, m, *trail), dtype=src.dtype, device=src.device)
+    # an empty source has no storage (a NULL pointer, which the entry point refuses) and no
+    # element the kernel could read: any valid pointer stands in for it
+    src_ptr = nat.ptr(out) if empty_src else nat.ptr(flat)
     # out-of-range indices: the device's deferred status word, raised at the next status
     # read (torch.gather on a HIP tensor raises a device-side assert that likewise
     # surfaces at the next sync); on the CPU (host build) the check is immediate
     host = src.device.type == "cpu"
     status = nat.scratch_status(src.device) if host else nat.deferred_status(src.device)
-    nat.call("co_gather_by_index", nat.ptr(flat), outer, flat.shape[1], inner * es,
+    nat.call("co_gather_by_index", src_ptr, outer, flat.shape[1], inner * es,
              flat.stride(0) * es, flat.stride(1) * es, nat.ptr(idx2), m, idx2.stride(0),
              idx2.stride(1), nat.ptr(out), nat.ptr(status), nat.stream_of(src))
     if host:
