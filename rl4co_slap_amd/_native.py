@@ -394,6 +394,15 @@ def check_rc(name, rc):
         raise RuntimeError(f"{name} failed with status {rc}")
 
 
+def glue_result(name, r):
+    """What a step-glue call returned: an int is the C ABI's status (raised through
+    ``check_rc``); anything else -- the outputs, or None for "stepped aside, nothing done"
+    -- is handed back."""
+    if type(r) is int:
+        check_rc(name, r)
+    return r
+
+
 def call(name, *args):
     fast = _fast if _fast else _fastcall()
     if args and args[-1] is HOST:
@@ -492,6 +501,21 @@ def raise_deferred(bits: int, device) -> None:
     for bit, msg in _DEFERRED_MSGS:
         if bits & bit:
             raise RuntimeError(msg)
+
+
+def read_status(words, device) -> list:
+    """The caller's int32 status ``words`` (tensors on ``device``, read in order) as ints,
+    in ONE host read that also carries the device's pending deferred word, whose error is
+    raised first (``raise_deferred``)."""
+    device = torch.device(device)
+    d = pending_deferred(device) if device.type != "cpu" else None
+    if d is not None:
+        words = [*words, d]
+    words = [w if w.dim() == 1 else w.reshape(-1) for w in words]
+    vals = (words[0] if len(words) == 1 else torch.cat(words)).tolist()
+    if d is not None:
+        raise_deferred(vals.pop(), device)
+    return vals
 
 
 def check_deferred(device) -> None:

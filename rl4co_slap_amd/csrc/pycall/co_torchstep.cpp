@@ -18,7 +18,6 @@
 
 #include <cstdint>
 #include <cstdlib>
-#include <cstring>
 #include <unordered_map>
 #include <vector>
 
@@ -208,6 +207,29 @@ struct Carver {
   }
 };
 
+// a step's action [B] int64 and log-probability [B] f32: the next two rows of g_slab
+struct ActLogp {
+  at::Tensor act, logp;
+};
+ActLogp take_act_logp(const c10::Device& dev, int64_t b, void* stream) {
+  const int64_t kb = up(8 * b);
+  const int64_t ko = g_slab.take(dev, 2 * kb, stream);
+  return {view_of(g_slab.st, at::kLong, ko, {b}), view_of(g_slab.st, at::kFloat, ko + kb, {b})};
+}
+
+// The operand tests every fused decode + env step makes besides its own state's (the
+// conditions the envs' Python decode_and_step checks before its launch): the state on a
+// CUDA device `dev` that logits and status share; logits f32 [b, width] with a unit inner
+// stride and at most 2048 columns; status int32; action_in (or none) int64, contiguous,
+// b elements.
+bool operands_fit(const c10::Device& dev, int64_t b, int64_t width, const at::Tensor& logits,
+                  const at::Tensor& status, const at::Tensor* ain) {
+  return dev.is_cuda() && logits.device() == dev && logits.scalar_type() == at::kFloat &&
+         logits.dim() == 2 && logits.stride(1) == 1 && logits.size(0) == b &&
+         logits.size(1) == width && width <= 2048 && status.device() == dev &&
+         status.scalar_type() == at::kInt && (!ain || fits(*ain, dev, at::kLong, b));
+}
+
 // The fused TSP decode step's operand checks, output memory and launch (shared by
 // tsp_decode_step and tsp_step_td).  Returns -1 when the operands do not fit (the caller's
 // Python path handles them), else the C ABI's status; out = act, logp, mask_out, i_out,
@@ -216,22 +238,15 @@ int tsp_launch(TspDecodeStep fn, const at::Tensor& logits, const at::Tensor& mas
                const at::Tensor& i, const at::Tensor* first, const at::Tensor* ain,
                const at::Tensor& status, double clip, double temp, long mode, uint64_t seed,
                uint64_t offset, long take, at::Tensor (&out)[7]) {
-  // the conditions envs/tsp.py:decode_and_step checks before its launch
   const c10::Device dev = mask.device();
-  if (!dev.is_cuda() || logits.device() != dev || i.device() != dev || status.device() != dev ||
-      logits.scalar_type() != at::kFloat || logits.dim() != 2 || logits.stride(1) != 1 ||
-      mask.dim() != 2 || mask.scalar_type() != at::kBool || !mask.is_contiguous() ||
-      i.scalar_type() != at::kLong || !i.is_contiguous() || status.scalar_type() != at::kInt)
-    return -1;
+  if (mask.dim() != 2 || mask.scalar_type() != at::kBool || !mask.is_contiguous()) return -1;
   const int64_t b = mask.size(0), nl = mask.size(1);
-  if (logits.size(0) != b || logits.size(1) != nl || nl > 2048 || i.numel() != b) return -1;
+  if (!operands_fit(dev, b, nl, logits, status, ain) || !fits(i, dev, at::kLong, b)) return -1;
   if (!take && (!first || !fits(*first, dev, at::kLong, b))) return -1;
-  if (ain && !fits(*ain, dev, at::kLong, b)) return -1;
-  const int64_t kb = up(8 * b);
   void* stream = current_stream(dev);
-  const int64_t ko = g_slab.take(dev, 2 * kb, stream);
-  out[0] = view_of(g_slab.st, at::kLong, ko, {b});
-  out[1] = view_of(g_slab.st, at::kFloat, ko + kb, {b});
+  ActLogp al = take_act_logp(dev, b, stream);
+  out[0] = std::move(al.act);
+  out[1] = std::move(al.logp);
   Carver c;
   const int64_t om = c.take(b * nl), oi = c.take(8 * b), of = c.take(8 * b), od = c.take(b),
                 orw = c.take(b);
@@ -261,11 +276,7 @@ int tsp_launch(TspDecodeStep fn, const at::Tensor& logits, const at::Tensor& mas
 //                 seed, offset, take) -> (act, logp, mask_out, i_out, first_out, done,
 //                 reward) | None | error code
 // fn: address of co_tsp_decode_step; first_in / action_in: tensor or None.
-PyObject* tsp_decode_step(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 13) {
-    PyErr_SetString(PyExc_TypeError, "tsp_decode_step: 13 arguments");
-    return nullptr;
-  }
+PyObject* tsp_decode_step(PyObject* const* a) {
   if (!is_tensor(a[1]) || !is_tensor(a[2]) || !is_tensor(a[3]) || !is_tensor(a[6]) ||
       (a[4] != Py_None && !is_tensor(a[4])) || (a[5] != Py_None && !is_tensor(a[5])))
     Py_RETURN_NONE;
@@ -276,20 +287,15 @@ PyObject* tsp_decode_step(PyObject*, PyObject* const* a, Py_ssize_t n) {
   const uint64_t offset = PyLong_AsUnsignedLongLongMask(a[11]);
   const long take = PyLong_AsLong(a[12]);
   if (PyErr_Occurred()) return nullptr;
-  try {
-    at::Tensor out[7];
-    const int rc = tsp_launch(fn, THPVariable_Unpack(a[1]), THPVariable_Unpack(a[2]),
-                              THPVariable_Unpack(a[3]),
-                              is_tensor(a[4]) ? &THPVariable_Unpack(a[4]) : nullptr,
-                              is_tensor(a[5]) ? &THPVariable_Unpack(a[5]) : nullptr,
-                              THPVariable_Unpack(a[6]), clip, temp, mode, seed, offset, take, out);
-    if (rc < 0) Py_RETURN_NONE;
-    if (rc != CO_OK) return PyLong_FromLong(rc);  // the caller raises _native's error
-    return wrap_all({&out[0], &out[1], &out[2], &out[3], &out[4], &out[5], &out[6]});
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
-    return nullptr;
-  }
+  at::Tensor out[7];
+  const int rc = tsp_launch(fn, THPVariable_Unpack(a[1]), THPVariable_Unpack(a[2]),
+                            THPVariable_Unpack(a[3]),
+                            is_tensor(a[4]) ? &THPVariable_Unpack(a[4]) : nullptr,
+                            is_tensor(a[5]) ? &THPVariable_Unpack(a[5]) : nullptr,
+                            THPVariable_Unpack(a[6]), clip, temp, mode, seed, offset, take, out);
+  if (rc < 0) Py_RETURN_NONE;
+  if (rc != CO_OK) return PyLong_FromLong(rc);  // the caller raises _native's error
+  return wrap_all({&out[0], &out[1], &out[2], &out[3], &out[4], &out[5], &out[6]});
 }
 
 // The td's keys as interned strings, made once per string literal (the literal's address
@@ -343,115 +349,49 @@ int remember(PyObject* t, PyObject* attr, long long value) {
   return r;
 }
 
-// tsp_step_td(fn, lb_attr, td, logits, mode, temp, clip, action_in, seed, offset, status,
-//             key) -> (action, logp) | None | error code
-// TSPEnv.decode_and_step on a dict-backed TensorDict: reads action_mask / i / first_node,
-// checks the env's knowledge of i (the batch-wide first-node test), launches, records
-// i + 1 and the done lower bound (attribute lb_attr) on the new state tensors and stores
-// the new state in the td -- what envs/tsp.py does around tsp_decode_step, without the
-// Python frames.  (fn, lb_attr) lead so that a functools.partial binds them.
-PyObject* tsp_step_td(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 12) {
-    PyErr_SetString(PyExc_TypeError, "tsp_step_td: 12 arguments");
-    return nullptr;
-  }
-  PyObject* td = a[2];
-  PyObject* lb_attr = a[1];
-  PyObject* key = a[11];
-  PyObject* ain_o = a[7];
-  if (!PyDict_Check(td) || !is_tensor(a[3]) || !is_tensor(a[10]) ||
-      (ain_o != Py_None && !is_tensor(ain_o)) || !PyUnicode_Check(key) ||
-      !PyUnicode_Check(lb_attr))
-    Py_RETURN_NONE;
-  PyObject* mask_o = PyDict_GetItem(td, key_of("action_mask"));  // borrowed
-  PyObject* i_o = PyDict_GetItem(td, key_of("i"));
-  if (!mask_o || !i_o || !is_tensor(mask_o) || !is_tensor(i_o)) Py_RETURN_NONE;
-  const long long k = known(i_o, g_attr_i);
-  if (k < 0) Py_RETURN_NONE;
-  const long take = k == 0 ? 1 : 0;
-  PyObject* first_o = take ? nullptr : PyDict_GetItem(td, key_of("first_node"));
-  if (!take && (!first_o || !is_tensor(first_o))) Py_RETURN_NONE;
-  const auto fn = fn_at<TspDecodeStep>(a[0]);
-  const long mode = PyLong_AsLong(a[4]);
-  const double temp = PyFloat_AsDouble(a[5]), clip = PyFloat_AsDouble(a[6]);
-  const uint64_t seed = PyLong_AsUnsignedLongLongMask(a[8]);
-  const uint64_t offset = PyLong_AsUnsignedLongLongMask(a[9]);
-  if (PyErr_Occurred()) return nullptr;
-  at::Tensor out[7];
-  try {
-    const int rc = tsp_launch(fn, THPVariable_Unpack(a[3]), THPVariable_Unpack(mask_o),
-                              THPVariable_Unpack(i_o),
-                              first_o ? &THPVariable_Unpack(first_o) : nullptr,
-                              ain_o != Py_None ? &THPVariable_Unpack(ain_o) : nullptr,
-                              THPVariable_Unpack(a[10]), clip, temp, mode, seed, offset, take,
-                              out);
-    if (rc < 0) Py_RETURN_NONE;
-    if (rc != CO_OK) return PyLong_FromLong(rc);
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
-    return nullptr;
-  }
-  const long long lb = known(mask_o, lb_attr);
-  PyObject* o[7];
-  for (int j = 0; j < 7; ++j) {
-    o[j] = THPVariable_Wrap(std::move(out[j]));
-    if (!o[j]) {
-      for (int q = 0; q < j; ++q) Py_DECREF(o[q]);
-      return nullptr;
-    }
-  }
-  PyObject* sel = ain_o != Py_None ? ain_o : o[0];
-  int err = remember(o[3], g_attr_i, k + 1);
-  if (!err && lb >= 0) err = remember(o[2], lb_attr, lb > 0 ? lb - 1 : 0);
-  if (!err) err = PyDict_SetItem(td, key, sel);
-  if (!err) err = PyDict_SetItem(td, key_of("first_node"), o[4]);
-  if (!err) err = PyDict_SetItem(td, key_of("current_node"), sel);
-  if (!err) err = PyDict_SetItem(td, key_of("i"), o[3]);
-  if (!err) err = PyDict_SetItem(td, key_of("action_mask"), o[2]);
-  if (!err) err = PyDict_SetItem(td, key_of("reward"), o[6]);
-  if (!err) err = PyDict_SetItem(td, key_of("done"), o[5]);
-  PyObject* res = err ? nullptr : PyTuple_Pack(2, sel, o[1]);
-  for (int j = 0; j < 7; ++j) Py_DECREF(o[j]);
-  return res;
-}
+// ---- what the three env *_step_td functions share ----------------------------------
+// The call (fn, lb_attr, td, logits, mode, temp, clip, action_in, seed, offset, status, key);
+// (fn, lb_attr) lead so that a functools.partial binds them.  parse() checks every
+// argument's type (false: step aside); scalars() converts the numbers (false: a Python
+// error is set), called after the env's own td reads so that a td the glue cannot take
+// steps aside first; fit() is operands_fit for the env's device, batch and logits width.
+struct StepCall {
+  PyObject* const* a;
+  PyObject *lb_attr, *td, *key, *ain_o;
+  const at::Tensor *logits, *status, *ain;
+  uintptr_t fn_addr;
+  long mode;
+  double temp, clip;
+  uint64_t seed, offset;
 
-// Wraps the 7 outputs, records i / lb, stores the new state in the td; shared tail of the
-// env step_td functions.  `extra` = (key, tensor) pairs to set besides the action key.
-PyObject* td_finish(PyObject* td, PyObject* key, PyObject* ain_o, at::Tensor& act,
-                    at::Tensor& logp, std::initializer_list<std::pair<const char*, at::Tensor*>> st,
-                    std::initializer_list<std::pair<const char*, PyObject*>> views,
-                    PyObject* lb_src, PyObject* lb_attr, const char* lb_dst) {
-  const long long lb = lb_src ? known(lb_src, lb_attr) : -1;
-  PyObject* a_o = THPVariable_Wrap(std::move(act));
-  PyObject* l_o = THPVariable_Wrap(std::move(logp));
-  if (!a_o || !l_o) {
-    Py_XDECREF(a_o);
-    Py_XDECREF(l_o);
-    return nullptr;
+  bool parse(PyObject* const* args) {
+    a = args;
+    lb_attr = a[1], td = a[2], ain_o = a[7], key = a[11];
+    if (!PyDict_Check(td) || !is_tensor(a[3]) || !is_tensor(a[10]) ||
+        (ain_o != Py_None && !is_tensor(ain_o)) || !PyUnicode_Check(key) ||
+        !PyUnicode_Check(lb_attr))
+      return false;
+    logits = &THPVariable_Unpack(a[3]);
+    status = &THPVariable_Unpack(a[10]);
+    ain = ain_o != Py_None ? &THPVariable_Unpack(ain_o) : nullptr;
+    return true;
   }
-  PyObject* sel = ain_o != Py_None ? ain_o : a_o;
-  int err = PyDict_SetItem(td, key, sel);
-  for (auto& kv : st) {
-    if (err) break;
-    PyObject* o = THPVariable_Wrap(std::move(*kv.second));
-    if (!o) {
-      err = -1;
-      break;
-    }
-    if (lb >= 0 && lb_dst && std::strcmp(kv.first, lb_dst) == 0)
-      err = remember(o, lb_attr, lb > 0 ? lb - 1 : 0);
-    if (!err) err = PyDict_SetItem(td, key_of(kv.first), o);
-    Py_DECREF(o);
+  bool scalars() {
+    fn_addr = static_cast<uintptr_t>(PyLong_AsUnsignedLongLongMask(a[0]));
+    mode = PyLong_AsLong(a[4]);
+    temp = PyFloat_AsDouble(a[5]), clip = PyFloat_AsDouble(a[6]);
+    seed = PyLong_AsUnsignedLongLongMask(a[8]);
+    offset = PyLong_AsUnsignedLongLongMask(a[9]);
+    return !PyErr_Occurred();
   }
-  for (auto& kv : views) {
-    if (err) break;
-    err = PyDict_SetItem(td, key_of(kv.first), kv.second);
+  template <class F>
+  F fn() const {
+    return reinterpret_cast<F>(fn_addr);
   }
-  PyObject* res = err ? nullptr : PyTuple_Pack(2, sel, l_o);
-  Py_DECREF(a_o);
-  Py_DECREF(l_o);
-  return res;
-}
+  bool fit(const c10::Device& dev, int64_t b, int64_t width) const {
+    return operands_fit(dev, b, width, *logits, *status, ain);
+  }
+};
 
 inline PyObject* td_tensor(PyObject* td, const char* k) {  // borrowed; nullptr if absent
   PyObject* o = PyDict_GetItem(td, key_of(k));
@@ -465,6 +405,83 @@ inline int set_wrapped(PyObject* td, const char* k, at::Tensor& t) {
   const int err = PyDict_SetItem(td, key_of(k), o);
   Py_DECREF(o);
   return err;
+}
+
+// a step clears / visits / places at most one: the done lower bound of the next state
+inline long long lb_next(long long lb) { return lb > 0 ? lb - 1 : 0; }
+
+struct TdEntry {  // td[key] = a new object of *fresh; without one, the selected action
+  const char* key;
+  at::Tensor* fresh = nullptr;
+};
+struct TdRecord {  // remember(td[key], attr, value)
+  const char* key;
+  PyObject* attr;
+  long long value;
+};
+
+// The tail of every *_step_td: td[key] = the selected action (action_in when given, else
+// the new action), then the entries in order (the dict insertion order users see), then
+// the host-side records on what the td now holds under their keys (so an entry written in
+// place, which its caller does not pass, is recorded like a fresh one).  Returns (selected
+// action, logp).  The two objects made here are released here on every path; set_wrapped
+// releases each entry's; `sel` and the record targets are borrowed.
+PyObject* td_finish(const StepCall& sc, at::Tensor& act, at::Tensor& logp,
+                    c10::ArrayRef<TdEntry> entries, c10::ArrayRef<TdRecord> records) {
+  PyObject* a_o = THPVariable_Wrap(std::move(act));
+  PyObject* l_o = a_o ? THPVariable_Wrap(std::move(logp)) : nullptr;
+  PyObject* res = nullptr;
+  if (l_o) {
+    PyObject* sel = sc.ain_o != Py_None ? sc.ain_o : a_o;
+    int err = PyDict_SetItem(sc.td, sc.key, sel);
+    for (const TdEntry& e : entries) {
+      if (err) break;
+      err = e.fresh ? set_wrapped(sc.td, e.key, *e.fresh)
+                    : PyDict_SetItem(sc.td, key_of(e.key), sel);
+    }
+    for (const TdRecord& r : records) {
+      if (err) break;
+      PyObject* o = PyDict_GetItem(sc.td, key_of(r.key));
+      err = o ? remember(o, r.attr, r.value) : -1;
+    }
+    if (!err) res = PyTuple_Pack(2, sel, l_o);
+  }
+  Py_XDECREF(a_o);
+  Py_XDECREF(l_o);
+  return res;
+}
+
+// tsp_step_td(fn, lb_attr, td, logits, mode, temp, clip, action_in, seed, offset, status,
+//             key) -> (action, logp) | None | error code
+// TSPEnv.decode_and_step on a dict-backed TensorDict: reads action_mask / i / first_node,
+// checks the env's knowledge of i (the batch-wide first-node test), launches, records
+// i + 1 and the done lower bound (attribute lb_attr) on the new state tensors and stores
+// the new state in the td -- what envs/tsp.py does around tsp_decode_step, without the
+// Python frames.
+PyObject* tsp_step_td(PyObject* const* a) {
+  StepCall sc;
+  if (!sc.parse(a)) Py_RETURN_NONE;
+  PyObject *mask_o = td_tensor(sc.td, "action_mask"), *i_o = td_tensor(sc.td, "i");
+  if (!mask_o || !i_o) Py_RETURN_NONE;
+  const long long k = known(i_o, g_attr_i);
+  if (k < 0) Py_RETURN_NONE;
+  const long take = k == 0 ? 1 : 0;
+  PyObject* first_o = take ? nullptr : td_tensor(sc.td, "first_node");
+  if (!take && !first_o) Py_RETURN_NONE;
+  if (!sc.scalars()) return nullptr;
+  at::Tensor out[7];
+  const int rc = tsp_launch(sc.fn<TspDecodeStep>(), *sc.logits, THPVariable_Unpack(mask_o),
+                            THPVariable_Unpack(i_o),
+                            first_o ? &THPVariable_Unpack(first_o) : nullptr, sc.ain, *sc.status,
+                            sc.clip, sc.temp, sc.mode, sc.seed, sc.offset, take, out);
+  if (rc < 0) Py_RETURN_NONE;
+  if (rc != CO_OK) return PyLong_FromLong(rc);
+  const long long lb = known(mask_o, sc.lb_attr);
+  const TdRecord recs[2] = {{"i", g_attr_i, k + 1}, {"action_mask", sc.lb_attr, lb_next(lb)}};
+  return td_finish(sc, out[0], out[1],
+                   {{"first_node", &out[4]}, {"current_node"}, {"i", &out[3]},
+                    {"action_mask", &out[2]}, {"reward", &out[6]}, {"done", &out[5]}},
+                   c10::ArrayRef<TdRecord>(recs, lb >= 0 ? 2 : 1));
 }
 
 // True when `o` (a tensor the td dict holds) is referenced by nothing but that dict: one
@@ -538,251 +555,191 @@ struct SlapBlock {
 //   place; otherwise the row is copied into a new storage of its own (so the next step can
 //   write it in place);
 // * the state block (SlapBlock) likewise: in place when held by the td alone.
-PyObject* slap_step_td(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 12) {
-    PyErr_SetString(PyExc_TypeError, "slap_step_td: 12 arguments");
-    return nullptr;
-  }
-  PyObject* lb_attr = a[1];
-  PyObject* td = a[2];
-  PyObject* key = a[11];
-  PyObject* ain_o = a[7];
-  if (!PyDict_Check(td) || !is_tensor(a[3]) || !is_tensor(a[10]) ||
-      (ain_o != Py_None && !is_tensor(ain_o)) || !PyUnicode_Check(key) || !PyUnicode_Check(lb_attr))
-    Py_RETURN_NONE;
-  PyObject *mask_o = td_tensor(td, "action_mask"), *i_o = td_tensor(td, "i"),
-           *tc_o = td_tensor(td, "to_choose"), *as_o = td_tensor(td, "assignment"),
-           *fr_o = td_tensor(td, "freq"), *dn_o = td_tensor(td, "done"),
-           *rw_o = td_tensor(td, "reward");
+PyObject* slap_step_td(PyObject* const* a) {
+  StepCall sc;
+  if (!sc.parse(a)) Py_RETURN_NONE;
+  PyObject *mask_o = td_tensor(sc.td, "action_mask"), *i_o = td_tensor(sc.td, "i"),
+           *tc_o = td_tensor(sc.td, "to_choose"), *as_o = td_tensor(sc.td, "assignment"),
+           *fr_o = td_tensor(sc.td, "freq"), *dn_o = td_tensor(sc.td, "done"),
+           *rw_o = td_tensor(sc.td, "reward");
   if (!mask_o || !i_o || !tc_o || !as_o || !fr_o) Py_RETURN_NONE;
-  const auto fn = fn_at<SlapDecodeStep>(a[0]);
   const long long ki = known(i_o, g_attr_i);
   const long long ktc = known(tc_o, g_attr_tc);
-  const long long lb = known(i_o, lb_attr);
-  const long mode = PyLong_AsLong(a[4]);
-  const double temp = PyFloat_AsDouble(a[5]), clip = PyFloat_AsDouble(a[6]);
-  const uint64_t seed = PyLong_AsUnsignedLongLongMask(a[8]);
-  const uint64_t offset = PyLong_AsUnsignedLongLongMask(a[9]);
-  if (PyErr_Occurred()) return nullptr;
-  try {
-    const at::Tensor& logits = THPVariable_Unpack(a[3]);
-    const at::Tensor& mask = THPVariable_Unpack(mask_o);
-    const at::Tensor& i = THPVariable_Unpack(i_o);
-    const at::Tensor& tc = THPVariable_Unpack(tc_o);
-    const at::Tensor& asg = THPVariable_Unpack(as_o);
-    const at::Tensor& status = THPVariable_Unpack(a[10]);
-    const at::Tensor* ain = ain_o != Py_None ? &THPVariable_Unpack(ain_o) : nullptr;
-    const c10::Device dev = mask.device();
-    // the conditions envs/slap.py:decode_and_step checks
-    if (!dev.is_cuda() || logits.device() != dev || logits.scalar_type() != at::kFloat ||
-        logits.dim() != 2 || logits.stride(1) != 1 || mask.dim() != 2 ||
-        mask.scalar_type() != at::kBool || !mask.is_contiguous() || tc.dim() != 2 ||
-        tc.device() != dev || tc.scalar_type() != at::kFloat || tc.stride(1) != 1 ||
-        tc.size(1) < 1 || status.device() != dev || status.scalar_type() != at::kInt)
-      Py_RETURN_NONE;
-    const at::Tensor& fr = THPVariable_Unpack(fr_o);
-    const int64_t b = mask.size(0), l = mask.size(1);
-    if (fr.dim() < 2) Py_RETURN_NONE;
-    const int64_t p = fr.size(fr.dim() - 2);
-    if (logits.size(0) != b || logits.size(1) != l || l > 2048 || tc.size(0) != b ||
-        !fits(i, dev, at::kLong, b) || !fits(asg, dev, at::kInt, b * p) || asg.dim() != 2 ||
-        asg.size(0) != b)
-      Py_RETURN_NONE;
-    if (ain && !fits(*ain, dev, at::kLong, b)) Py_RETURN_NONE;
-    // the untouched arange: to_choose[:, 0] == k in every row (k + remaining columns == P)
-    const bool uniform = ktc >= 0 && ktc < p && ktc + tc.size(1) == p;
-    void* stream = current_stream(dev);
-    // in place only in the stream order of the previous step's launch (which made the
-    // tensors or last read them)
-    const bool same_stream = stream == g_slap_stream;
-    g_slap_stream = stream;
-    const bool asg_here = same_stream && exclusively_held(as_o, asg);
-    const SlapBlock blk(b, l);
-    bool blk_here = false;
-    if (same_stream && dn_o && rw_o) {
-      PyObject* const os[4] = {mask_o, i_o, dn_o, rw_o};
-      const at::Tensor* const ts[4] = {&mask, &i, &THPVariable_Unpack(dn_o), &THPVariable_Unpack(rw_o)};
-      blk_here = blk.held_alone(os, ts, b, l);
-    }
-    const int64_t kb = up(8 * b);
-    const int64_t ko = g_slab.take(dev, 2 * kb, stream);
-    at::Tensor act = view_of(g_slab.st, at::kLong, ko, {b});
-    at::Tensor logp = view_of(g_slab.st, at::kFloat, ko + kb, {b});
-    at::Tensor asg_out = asg_here ? asg : view_of(new_storage(dev, 4 * b * p), at::kInt, 0,
-                                                  asg.sizes());
-    at::Tensor mask_out, i_out, done, reward;
-    if (blk_here) {
-      mask_out = mask;
-      i_out = i;
-      done = THPVariable_Unpack(dn_o);
-      reward = THPVariable_Unpack(rw_o);
-    } else {
-      const c10::Storage st = new_storage(dev, blk.nbytes);
-      mask_out = view_of(st, at::kBool, blk.om, {b, l});
-      i_out = view_of(st, at::kLong, blk.oi, {b, 1});
-      done = view_of(st, at::kBool, blk.od, {b, 1});
-      reward = view_of(st, at::kBool, blk.orw, {b, 1});
-    }
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = fn(b, l, p, logits.const_data_ptr<float>(), logits.stride(0),
-            static_cast<const uint8_t*>(mask.const_data_ptr()), (float)clip, (float)temp, (int)mode,
-            ain ? ain->const_data_ptr<int64_t>() : nullptr, act.mutable_data_ptr<int64_t>(),
-            logp.mutable_data_ptr<float>(), seed, offset,
-            uniform ? nullptr : tc.const_data_ptr<float>(), uniform ? ktc : tc.stride(0),
-            asg.const_data_ptr<int32_t>(), asg_out.mutable_data_ptr<int32_t>(),
-            static_cast<uint8_t*>(mask_out.mutable_data_ptr()), i.const_data_ptr<int64_t>(),
-            i_out.mutable_data_ptr<int64_t>(), static_cast<uint8_t*>(done.mutable_data_ptr()),
-            static_cast<uint8_t*>(reward.mutable_data_ptr()), nullptr,
-            status.mutable_data_ptr<int32_t>(), stream);
-    Py_END_ALLOW_THREADS
-    if (rc != CO_OK) return PyLong_FromLong(rc);
-    if (asg_here) asg.unsafeGetTensorImpl()->bump_version();  // in-place writes
-    if (blk_here) {
-      mask.unsafeGetTensorImpl()->bump_version();
-      i.unsafeGetTensorImpl()->bump_version();
-      done.unsafeGetTensorImpl()->bump_version();
-      reward.unsafeGetTensorImpl()->bump_version();
-    }
-    PyObject* tc_next = THPVariable_Wrap(drop_first_col(tc));  // to_choose[:, 1:]
-    if (!tc_next) return nullptr;
-    int err = uniform ? remember(tc_next, g_attr_tc, ktc + 1) : 0;
-    if (!err) err = PyDict_SetItem(td, key_of("to_choose"), tc_next);
-    Py_DECREF(tc_next);
-    if (err) return nullptr;
-    PyObject* a_o = THPVariable_Wrap(std::move(act));
-    PyObject* l_o = a_o ? THPVariable_Wrap(std::move(logp)) : nullptr;
-    if (!a_o || !l_o) {
-      Py_XDECREF(a_o);
-      return nullptr;
-    }
-    PyObject* sel = ain_o != Py_None ? ain_o : a_o;
-    err = PyDict_SetItem(td, key, sel);
-    if (!err && !asg_here) err = set_wrapped(td, "assignment", asg_out);
-    if (!err && !blk_here) {
-      err = set_wrapped(td, "action_mask", mask_out);
-      if (!err) err = set_wrapped(td, "i", i_out);
-      if (!err) err = set_wrapped(td, "reward", reward);
-      if (!err) err = set_wrapped(td, "done", done);
-    }
-    // records on the new i / done: the done lower bound (lb - 1), and -- i uniform over the
-    // batch when the env knows its value (reset: 0; each step +1) -- i + 1 and done = (i ==
-    // P-1), so poll_done answers without a read
-    if (!err) {
-      PyObject* i_n = PyDict_GetItem(td, key_of("i"));
-      PyObject* d_n = PyDict_GetItem(td, key_of("done"));
-      if (!i_n || !d_n) err = -1;
-      if (!err && lb >= 0) err = remember(i_n, lb_attr, lb > 0 ? lb - 1 : 0);
-      if (!err && ki >= 0) {
-        err = remember(i_n, g_attr_i, ki + 1);
-        if (!err) err = remember(d_n, g_attr_i, ki == p - 1 ? 1 : 0);
-      }
-    }
-    PyObject* res = err ? nullptr : PyTuple_Pack(2, sel, l_o);
-    Py_DECREF(a_o);
-    Py_DECREF(l_o);
-    return res;
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
-    return nullptr;
+  const long long lb = known(i_o, sc.lb_attr);
+  if (!sc.scalars()) return nullptr;
+  const at::Tensor& mask = THPVariable_Unpack(mask_o);
+  const at::Tensor& i = THPVariable_Unpack(i_o);
+  const at::Tensor& tc = THPVariable_Unpack(tc_o);
+  const at::Tensor& asg = THPVariable_Unpack(as_o);
+  const at::Tensor& fr = THPVariable_Unpack(fr_o);
+  const c10::Device dev = mask.device();
+  // the state conditions envs/slap.py:decode_and_step checks
+  if (mask.dim() != 2 || mask.scalar_type() != at::kBool || !mask.is_contiguous() ||
+      tc.dim() != 2 || tc.device() != dev || tc.scalar_type() != at::kFloat ||
+      tc.stride(1) != 1 || tc.size(1) < 1 || fr.dim() < 2)
+    Py_RETURN_NONE;
+  const int64_t b = mask.size(0), l = mask.size(1), p = fr.size(fr.dim() - 2);
+  if (!sc.fit(dev, b, l) || tc.size(0) != b || !fits(i, dev, at::kLong, b) ||
+      !fits(asg, dev, at::kInt, b * p) || asg.dim() != 2 || asg.size(0) != b)
+    Py_RETURN_NONE;
+  // the untouched arange: to_choose[:, 0] == k in every row (k + remaining columns == P)
+  const bool uniform = ktc >= 0 && ktc < p && ktc + tc.size(1) == p;
+  void* stream = current_stream(dev);
+  // in place only in the stream order of the previous step's launch (which made the
+  // tensors or last read them)
+  const bool same_stream = stream == g_slap_stream;
+  g_slap_stream = stream;
+  const bool asg_here = same_stream && exclusively_held(as_o, asg);
+  const SlapBlock blk(b, l);
+  bool blk_here = false;
+  if (same_stream && dn_o && rw_o) {
+    PyObject* const os[4] = {mask_o, i_o, dn_o, rw_o};
+    const at::Tensor* const ts[4] = {&mask, &i, &THPVariable_Unpack(dn_o), &THPVariable_Unpack(rw_o)};
+    blk_here = blk.held_alone(os, ts, b, l);
   }
+  ActLogp al = take_act_logp(dev, b, stream);
+  at::Tensor asg_out = asg_here ? asg : view_of(new_storage(dev, 4 * b * p), at::kInt, 0,
+                                                asg.sizes());
+  at::Tensor mask_out, i_out, done, reward;
+  if (blk_here) {
+    mask_out = mask;
+    i_out = i;
+    done = THPVariable_Unpack(dn_o);
+    reward = THPVariable_Unpack(rw_o);
+  } else {
+    const c10::Storage st = new_storage(dev, blk.nbytes);
+    mask_out = view_of(st, at::kBool, blk.om, {b, l});
+    i_out = view_of(st, at::kLong, blk.oi, {b, 1});
+    done = view_of(st, at::kBool, blk.od, {b, 1});
+    reward = view_of(st, at::kBool, blk.orw, {b, 1});
+  }
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = sc.fn<SlapDecodeStep>()(
+      b, l, p, sc.logits->const_data_ptr<float>(), sc.logits->stride(0),
+      static_cast<const uint8_t*>(mask.const_data_ptr()), (float)sc.clip, (float)sc.temp,
+      (int)sc.mode, sc.ain ? sc.ain->const_data_ptr<int64_t>() : nullptr,
+      al.act.mutable_data_ptr<int64_t>(), al.logp.mutable_data_ptr<float>(), sc.seed, sc.offset,
+      uniform ? nullptr : tc.const_data_ptr<float>(), uniform ? ktc : tc.stride(0),
+      asg.const_data_ptr<int32_t>(), asg_out.mutable_data_ptr<int32_t>(),
+      static_cast<uint8_t*>(mask_out.mutable_data_ptr()), i.const_data_ptr<int64_t>(),
+      i_out.mutable_data_ptr<int64_t>(), static_cast<uint8_t*>(done.mutable_data_ptr()),
+      static_cast<uint8_t*>(reward.mutable_data_ptr()), nullptr,
+      sc.status->mutable_data_ptr<int32_t>(), stream);
+  Py_END_ALLOW_THREADS
+  if (rc != CO_OK) return PyLong_FromLong(rc);
+  if (asg_here) asg.unsafeGetTensorImpl()->bump_version();  // in-place writes
+  if (blk_here) {
+    mask.unsafeGetTensorImpl()->bump_version();
+    i.unsafeGetTensorImpl()->bump_version();
+    done.unsafeGetTensorImpl()->bump_version();
+    reward.unsafeGetTensorImpl()->bump_version();
+  }
+  PyObject* tc_next = THPVariable_Wrap(drop_first_col(tc));  // to_choose[:, 1:]
+  if (!tc_next) return nullptr;
+  int err = uniform ? remember(tc_next, g_attr_tc, ktc + 1) : 0;
+  if (!err) err = PyDict_SetItem(sc.td, key_of("to_choose"), tc_next);
+  Py_DECREF(tc_next);
+  if (err) return nullptr;
+  // the entries not written in place
+  TdEntry ents[5];
+  size_t ne = 0;
+  if (!asg_here) ents[ne++] = {"assignment", &asg_out};
+  if (!blk_here) {
+    ents[ne++] = {"action_mask", &mask_out};
+    ents[ne++] = {"i", &i_out};
+    ents[ne++] = {"reward", &reward};
+    ents[ne++] = {"done", &done};
+  }
+  // records on the new i / done: the done lower bound (lb - 1), and -- i uniform over the
+  // batch when the env knows its value (reset: 0; each step +1) -- i + 1 and done = (i ==
+  // P-1), so poll_done answers without a read
+  TdRecord recs[3];
+  size_t nr = 0;
+  if (lb >= 0) recs[nr++] = {"i", sc.lb_attr, lb_next(lb)};
+  if (ki >= 0) {
+    recs[nr++] = {"i", g_attr_i, ki + 1};
+    recs[nr++] = {"done", g_attr_i, ki == p - 1 ? 1 : 0};
+  }
+  return td_finish(sc, al.act, al.logp, c10::ArrayRef<TdEntry>(ents, ne),
+                   c10::ArrayRef<TdRecord>(recs, nr));
 }
+
+// The CVRP step's state block: used capacity, visited, current node [B, 1], done [B],
+// reward [B], action_mask [B, N+1] carved from one pooled storage (g_state).
+struct CvrpBlock {
+  int64_t ou, ov, oc, od, orw, om;
+  at::Tensor used, visited, cur, done, reward, mask;
+  CvrpBlock(const c10::Device& dev, int64_t b, int64_t nl, const at::Tensor& used_in,
+            const at::Tensor& visited_in, void* stream) {
+    Carver c;
+    ou = c.take(4 * b), ov = c.take(b * (nl + 1)), oc = c.take(8 * b), od = c.take(b);
+    orw = c.take(b), om = c.take(b * (nl + 1));
+    const c10::Storage st = g_state.acquire(dev, c.off, stream);
+    used = view_of(st, at::kFloat, ou, used_in.sizes());
+    visited = view_of(st, at::kByte, ov, visited_in.sizes());
+    cur = view_of(st, at::kLong, oc, {b, 1});
+    done = view_of(st, at::kBool, od, {b});
+    reward = view_of(st, at::kBool, orw, {b});
+    mask = view_of(st, at::kBool, om, {b, nl + 1});
+  }
+};
 
 // cvrp_step_td(fn, lb_attr, td, logits, mode, temp, clip, action_in, seed, offset, status,
 //              key) -> (action, logp) | None | error code
 // CVRPEnv.decode_and_step (envs/cvrp.py) on a dict-backed TensorDict in one call.
-PyObject* cvrp_step_td(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 12) {
-    PyErr_SetString(PyExc_TypeError, "cvrp_step_td: 12 arguments");
-    return nullptr;
-  }
-  PyObject* lb_attr = a[1];
-  PyObject* td = a[2];
-  PyObject* key = a[11];
-  PyObject* ain_o = a[7];
-  if (!PyDict_Check(td) || !is_tensor(a[3]) || !is_tensor(a[10]) ||
-      (ain_o != Py_None && !is_tensor(ain_o)) || !PyUnicode_Check(key) || !PyUnicode_Check(lb_attr))
-    Py_RETURN_NONE;
-  PyObject *mask_o = td_tensor(td, "action_mask"), *dem_o = td_tensor(td, "demand"),
-           *used_o = td_tensor(td, "used_capacity"), *cap_o = td_tensor(td, "vehicle_capacity"),
-           *vis_o = td_tensor(td, "visited");
+PyObject* cvrp_step_td(PyObject* const* a) {
+  StepCall sc;
+  if (!sc.parse(a)) Py_RETURN_NONE;
+  PyObject *mask_o = td_tensor(sc.td, "action_mask"), *dem_o = td_tensor(sc.td, "demand"),
+           *used_o = td_tensor(sc.td, "used_capacity"),
+           *cap_o = td_tensor(sc.td, "vehicle_capacity"), *vis_o = td_tensor(sc.td, "visited");
   if (!mask_o || !dem_o || !used_o || !cap_o || !vis_o) Py_RETURN_NONE;
-  const auto fn = fn_at<CvrpDecodeStep>(a[0]);
-  const long mode = PyLong_AsLong(a[4]);
-  const double temp = PyFloat_AsDouble(a[5]), clip = PyFloat_AsDouble(a[6]);
-  const uint64_t seed = PyLong_AsUnsignedLongLongMask(a[8]);
-  const uint64_t offset = PyLong_AsUnsignedLongLongMask(a[9]);
-  if (PyErr_Occurred()) return nullptr;
-  try {
-    const at::Tensor& logits = THPVariable_Unpack(a[3]);
-    const at::Tensor& mask = THPVariable_Unpack(mask_o);
-    const at::Tensor& dem = THPVariable_Unpack(dem_o);
-    const at::Tensor& used = THPVariable_Unpack(used_o);
-    const at::Tensor& cap = THPVariable_Unpack(cap_o);
-    const at::Tensor& vis = THPVariable_Unpack(vis_o);
-    const at::Tensor& status = THPVariable_Unpack(a[10]);
-    const at::Tensor* ain = ain_o != Py_None ? &THPVariable_Unpack(ain_o) : nullptr;
-    const c10::Device dev = dem.device();
-    if (!dev.is_cuda() || dem.dim() != 2 || logits.device() != dev ||
-        logits.scalar_type() != at::kFloat || logits.dim() != 2 || logits.stride(1) != 1 ||
-        status.device() != dev || status.scalar_type() != at::kInt)
-      Py_RETURN_NONE;
-    const int64_t b = dem.size(0), nl = dem.size(1);
-    if (logits.size(0) != b || logits.size(1) != nl + 1 || nl + 1 > 2048 ||
-        !fits(dem, dev, at::kFloat) || !fits(used, dev, at::kFloat, b) ||
-        !fits(cap, dev, at::kFloat, b) || !fits(vis, dev, at::kByte, b * (nl + 1)) ||
-        !fits(mask, dev, at::kBool, b * (nl + 1)) || mask.dim() != 2)
-      Py_RETURN_NONE;
-    if (ain && !fits(*ain, dev, at::kLong, b)) Py_RETURN_NONE;
-    const int64_t kb = up(8 * b);
-    void* stream = current_stream(dev);
-    const int64_t ko = g_slab.take(dev, 2 * kb, stream);
-    at::Tensor act = view_of(g_slab.st, at::kLong, ko, {b});
-    at::Tensor logp = view_of(g_slab.st, at::kFloat, ko + kb, {b});
-    Carver c;
-    const int64_t ou = c.take(4 * b), ov = c.take(b * (nl + 1)), oc = c.take(8 * b),
-                  od = c.take(b), orw = c.take(b), om = c.take(b * (nl + 1));
-    const c10::Storage st = g_state.acquire(dev, c.off, stream);
-    at::Tensor used_out = view_of(st, at::kFloat, ou, used.sizes());
-    at::Tensor vis_out = view_of(st, at::kByte, ov, vis.sizes());
-    at::Tensor cur = view_of(st, at::kLong, oc, {b, 1});
-    at::Tensor done = view_of(st, at::kBool, od, {b});
-    at::Tensor reward = view_of(st, at::kBool, orw, {b});
-    at::Tensor mask_out = view_of(st, at::kBool, om, {b, nl + 1});
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = fn(b, nl, logits.const_data_ptr<float>(), logits.stride(0),
-            static_cast<const uint8_t*>(mask.const_data_ptr()), (float)clip, (float)temp, (int)mode,
-            ain ? ain->const_data_ptr<int64_t>() : nullptr, act.mutable_data_ptr<int64_t>(),
-            logp.mutable_data_ptr<float>(), seed, offset, dem.const_data_ptr<float>(),
-            used.const_data_ptr<float>(), used_out.mutable_data_ptr<float>(),
-            cap.const_data_ptr<float>(), vis.const_data_ptr<uint8_t>(),
-            vis_out.mutable_data_ptr<uint8_t>(), cur.mutable_data_ptr<int64_t>(),
-            static_cast<uint8_t*>(done.mutable_data_ptr()),
-            static_cast<uint8_t*>(reward.mutable_data_ptr()),
-            static_cast<uint8_t*>(mask_out.mutable_data_ptr()), nullptr,
-            status.mutable_data_ptr<int32_t>(), stream);
-    Py_END_ALLOW_THREADS
-    if (rc != CO_OK) return PyLong_FromLong(rc);
-    return td_finish(td, key, ain_o, act, logp,
-                     {{"current_node", &cur}, {"used_capacity", &used_out},
-                      {"visited", &vis_out}, {"reward", &reward}, {"done", &done},
-                      {"action_mask", &mask_out}},
-                     {}, vis_o, lb_attr, "visited");
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
-    return nullptr;
-  }
+  if (!sc.scalars()) return nullptr;
+  const at::Tensor& mask = THPVariable_Unpack(mask_o);
+  const at::Tensor& dem = THPVariable_Unpack(dem_o);
+  const at::Tensor& used = THPVariable_Unpack(used_o);
+  const at::Tensor& cap = THPVariable_Unpack(cap_o);
+  const at::Tensor& vis = THPVariable_Unpack(vis_o);
+  const c10::Device dev = dem.device();
+  if (dem.dim() != 2) Py_RETURN_NONE;
+  const int64_t b = dem.size(0), nl = dem.size(1);
+  if (!sc.fit(dev, b, nl + 1) || !fits(dem, dev, at::kFloat) || !fits(used, dev, at::kFloat, b) ||
+      !fits(cap, dev, at::kFloat, b) || !fits(vis, dev, at::kByte, b * (nl + 1)) ||
+      !fits(mask, dev, at::kBool, b * (nl + 1)) || mask.dim() != 2)
+    Py_RETURN_NONE;
+  void* stream = current_stream(dev);
+  ActLogp al = take_act_logp(dev, b, stream);
+  CvrpBlock blk(dev, b, nl, used, vis, stream);
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = sc.fn<CvrpDecodeStep>()(
+      b, nl, sc.logits->const_data_ptr<float>(), sc.logits->stride(0),
+      static_cast<const uint8_t*>(mask.const_data_ptr()), (float)sc.clip, (float)sc.temp,
+      (int)sc.mode, sc.ain ? sc.ain->const_data_ptr<int64_t>() : nullptr,
+      al.act.mutable_data_ptr<int64_t>(), al.logp.mutable_data_ptr<float>(), sc.seed, sc.offset,
+      dem.const_data_ptr<float>(), used.const_data_ptr<float>(),
+      blk.used.mutable_data_ptr<float>(), cap.const_data_ptr<float>(),
+      vis.const_data_ptr<uint8_t>(), blk.visited.mutable_data_ptr<uint8_t>(),
+      blk.cur.mutable_data_ptr<int64_t>(), static_cast<uint8_t*>(blk.done.mutable_data_ptr()),
+      static_cast<uint8_t*>(blk.reward.mutable_data_ptr()),
+      static_cast<uint8_t*>(blk.mask.mutable_data_ptr()), nullptr,
+      sc.status->mutable_data_ptr<int32_t>(), stream);
+  Py_END_ALLOW_THREADS
+  if (rc != CO_OK) return PyLong_FromLong(rc);
+  const long long lb = known(vis_o, sc.lb_attr);
+  const TdRecord rec{"visited", sc.lb_attr, lb_next(lb)};
+  return td_finish(sc, al.act, al.logp,
+                   {{"current_node", &blk.cur}, {"used_capacity", &blk.used},
+                    {"visited", &blk.visited}, {"reward", &blk.reward}, {"done", &blk.done},
+                    {"action_mask", &blk.mask}},
+                   c10::ArrayRef<TdRecord>(&rec, lb >= 0 ? 1 : 0));
 }
 
 // decode_step(fn, logits, mask, action_in, status, clip, temp, mode, seed, offset, full)
 //   -> (act, logp, full_logprobs | None) | None
 // fn: address of co_decode_step (utils/decoding.py:decode_step without top-k / top-p)
-PyObject* decode_step(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 11) {
-    PyErr_SetString(PyExc_TypeError, "decode_step: 11 arguments");
-    return nullptr;
-  }
+PyObject* decode_step(PyObject* const* a) {
   if (!is_tensor(a[1])) Py_RETURN_NONE;
   const auto fn = fn_at<DecodeStep>(a[0]);
   const at::Tensor& logits = THPVariable_Unpack(a[1]);
@@ -797,57 +754,36 @@ PyObject* decode_step(PyObject*, PyObject* const* a, Py_ssize_t n) {
       logits.stride(1) != 1)
     Py_RETURN_NONE;
   const int64_t b = logits.size(0), nl = logits.size(1);
-  const at::Tensor *mask = nullptr, *ain = nullptr, *status = nullptr;
-  if (is_tensor(a[2])) {
-    mask = &THPVariable_Unpack(a[2]);
-    if (!fits(*mask, dev, at::kBool, b * nl) || mask->dim() != 2) Py_RETURN_NONE;
-  } else if (a[2] != Py_None) {
+  // mask / action_in / status: each a tensor that fits, or None
+  for (int k = 2; k <= 4; ++k)
+    if (a[k] != Py_None && !is_tensor(a[k])) Py_RETURN_NONE;
+  const at::Tensor* mask = a[2] != Py_None ? &THPVariable_Unpack(a[2]) : nullptr;
+  const at::Tensor* ain = a[3] != Py_None ? &THPVariable_Unpack(a[3]) : nullptr;
+  const at::Tensor* status = a[4] != Py_None ? &THPVariable_Unpack(a[4]) : nullptr;
+  if ((mask && (!fits(*mask, dev, at::kBool, b * nl) || mask->dim() != 2)) ||
+      (ain && !fits(*ain, dev, at::kLong, b)) || (status && !fits(*status, dev, at::kInt)))
     Py_RETURN_NONE;
-  }
-  if (is_tensor(a[3])) {
-    ain = &THPVariable_Unpack(a[3]);
-    if (!fits(*ain, dev, at::kLong, b)) Py_RETURN_NONE;
-  } else if (a[3] != Py_None) {
-    Py_RETURN_NONE;
-  }
-  if (is_tensor(a[4])) {
-    status = &THPVariable_Unpack(a[4]);
-    if (!fits(*status, dev, at::kInt)) Py_RETURN_NONE;
-  } else if (a[4] != Py_None) {
-    Py_RETURN_NONE;
-  }
-  try {
-    const int64_t kb = up(8 * b);
-    void* stream = current_stream(dev);
-    const int64_t ko = g_slab.take(dev, 2 * kb, stream);
-    at::Tensor act = view_of(g_slab.st, at::kLong, ko, {b});
-    at::Tensor logp = view_of(g_slab.st, at::kFloat, ko + kb, {b}), full;
-    if (want_full) full = at::empty({b, nl}, logits.options());
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = fn(b, nl, logits.const_data_ptr<float>(), logits.stride(0),
-            mask ? static_cast<const uint8_t*>(mask->const_data_ptr()) : nullptr, (float)clip,
-            (float)temp, (int)mode, ain ? ain->const_data_ptr<int64_t>() : nullptr,
-            act.mutable_data_ptr<int64_t>(), logp.mutable_data_ptr<float>(),
-            want_full ? full.mutable_data_ptr<float>() : nullptr, seed, offset,
-            status ? status->mutable_data_ptr<int32_t>() : nullptr, stream);
-    Py_END_ALLOW_THREADS
-    if (rc != CO_OK) return PyLong_FromLong(rc);
-    return wrap_all({&act, &logp, &full});
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
-    return nullptr;
-  }
+  void* stream = current_stream(dev);
+  ActLogp al = take_act_logp(dev, b, stream);
+  at::Tensor full;
+  if (want_full) full = at::empty({b, nl}, logits.options());
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = fn(b, nl, logits.const_data_ptr<float>(), logits.stride(0),
+          mask ? static_cast<const uint8_t*>(mask->const_data_ptr()) : nullptr, (float)clip,
+          (float)temp, (int)mode, ain ? ain->const_data_ptr<int64_t>() : nullptr,
+          al.act.mutable_data_ptr<int64_t>(), al.logp.mutable_data_ptr<float>(),
+          want_full ? full.mutable_data_ptr<float>() : nullptr, seed, offset,
+          status ? status->mutable_data_ptr<int32_t>() : nullptr, stream);
+  Py_END_ALLOW_THREADS
+  if (rc != CO_OK) return PyLong_FromLong(rc);
+  return wrap_all({&al.act, &al.logp, &full});
 }
 
 // cvrp_step(fn, action, demand, used, vehicle_capacity, visited)
 //   -> (used_out, visited_out, current_node, done, reward, action_mask) | None
 // fn: address of co_cvrp_step (envs/cvrp.py:_step)
-PyObject* cvrp_step(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 6) {
-    PyErr_SetString(PyExc_TypeError, "cvrp_step: 6 arguments");
-    return nullptr;
-  }
+PyObject* cvrp_step(PyObject* const* a) {
   for (int k = 1; k < 6; ++k)
     if (!is_tensor(a[k])) Py_RETURN_NONE;
   const auto fn = fn_at<CvrpStep>(a[0]);
@@ -864,44 +800,26 @@ PyObject* cvrp_step(PyObject*, PyObject* const* a, Py_ssize_t n) {
       !fits(used, dev, at::kFloat, b) || !fits(vcap, dev, at::kFloat, b) ||
       !fits(visited, dev, at::kByte, b * (nl + 1)))
     Py_RETURN_NONE;
-  try {
-    Carver c;
-    const int64_t ou = c.take(4 * b), ov = c.take(b * (nl + 1)), oc = c.take(8 * b),
-                  od = c.take(b), orw = c.take(b), om = c.take(b * (nl + 1));
-    void* stream = current_stream(dev);
-    const c10::Storage st = g_state.acquire(dev, c.off, stream);
-    at::Tensor used_out = view_of(st, at::kFloat, ou, used.sizes());
-    at::Tensor visited_out = view_of(st, at::kByte, ov, visited.sizes());
-    at::Tensor cur = view_of(st, at::kLong, oc, {b, 1});
-    at::Tensor done = view_of(st, at::kBool, od, {b});
-    at::Tensor reward = view_of(st, at::kBool, orw, {b});
-    at::Tensor mask = view_of(st, at::kBool, om, {b, nl + 1});
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = fn(b, nl, action.const_data_ptr<int64_t>(), demand.const_data_ptr<float>(),
-            used.const_data_ptr<float>(), used_out.mutable_data_ptr<float>(),
-            vcap.const_data_ptr<float>(), visited.const_data_ptr<uint8_t>(),
-            visited_out.mutable_data_ptr<uint8_t>(), cur.mutable_data_ptr<int64_t>(),
-            static_cast<uint8_t*>(done.mutable_data_ptr()),
-            static_cast<uint8_t*>(reward.mutable_data_ptr()),
-            static_cast<uint8_t*>(mask.mutable_data_ptr()), nullptr, nullptr, stream);
-    Py_END_ALLOW_THREADS
-    if (rc != CO_OK) return PyLong_FromLong(rc);
-    return wrap_all({&used_out, &visited_out, &cur, &done, &reward, &mask});
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
-    return nullptr;
-  }
+  void* stream = current_stream(dev);
+  CvrpBlock blk(dev, b, nl, used, visited, stream);
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = fn(b, nl, action.const_data_ptr<int64_t>(), demand.const_data_ptr<float>(),
+          used.const_data_ptr<float>(), blk.used.mutable_data_ptr<float>(),
+          vcap.const_data_ptr<float>(), visited.const_data_ptr<uint8_t>(),
+          blk.visited.mutable_data_ptr<uint8_t>(), blk.cur.mutable_data_ptr<int64_t>(),
+          static_cast<uint8_t*>(blk.done.mutable_data_ptr()),
+          static_cast<uint8_t*>(blk.reward.mutable_data_ptr()),
+          static_cast<uint8_t*>(blk.mask.mutable_data_ptr()), nullptr, nullptr, stream);
+  Py_END_ALLOW_THREADS
+  if (rc != CO_OK) return PyLong_FromLong(rc);
+  return wrap_all({&blk.used, &blk.visited, &blk.cur, &blk.done, &blk.reward, &blk.mask});
 }
 
 // slab_fresh(steps) -> None: the next step's action / log-probability rows start a new
 // slab storage sized for `steps` steps (DecodingStrategy calls it at an episode's first
 // step with the env's bound on the episode length)
-PyObject* slab_fresh(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 1) {
-    PyErr_SetString(PyExc_TypeError, "slab_fresh: 1 argument");
-    return nullptr;
-  }
+PyObject* slab_fresh(PyObject* const* a) {
   const long long steps = PyLong_AsLongLong(a[0]);
   if (PyErr_Occurred()) return nullptr;
   g_slab.fresh_steps = steps < 1 ? 1 : (steps > 4096 ? 4096 : steps);
@@ -915,11 +833,7 @@ PyObject* slab_fresh(PyObject*, PyObject* const* a, Py_ssize_t n) {
 // status) as one co_episode_stack launch -- when the two lists hold [B] tensors that are
 // consecutive rows of step-major slabs (what the step calls above return); None otherwise
 // (the caller stacks as before).
-PyObject* episode_stack(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 5) {
-    PyErr_SetString(PyExc_TypeError, "episode_stack: 5 arguments");
-    return nullptr;
-  }
+PyObject* episode_stack(PyObject* const* a) {
   PyObject *al = a[1], *ll_ = a[2];
   if (!PyList_Check(al) || !PyList_Check(ll_) || !is_tensor(a[3])) Py_RETURN_NONE;
   const Py_ssize_t T = PyList_GET_SIZE(al);
@@ -927,70 +841,65 @@ PyObject* episode_stack(PyObject*, PyObject* const* a, Py_ssize_t n) {
   const auto fn = fn_at<EpisodeStack>(a[0]);
   const int want_ll = PyObject_IsTrue(a[4]);
   if (want_ll < 0) return nullptr;
-  try {
-    const at::Tensor& status = THPVariable_Unpack(a[3]);
-    // the rows: [B] tensors, one storage per list, a uniform stride between steps
-    int64_t b = -1, rs[2] = {0, 0};
-    const void* base[2] = {nullptr, nullptr};
-    c10::Device dev{c10::DeviceType::CPU};
-    for (int li = 0; li < 2; ++li) {
-      PyObject* lst = li == 0 ? al : ll_;
-      const at::ScalarType dt = li == 0 ? at::kLong : at::kFloat;
-      const int64_t esz = li == 0 ? 8 : 4;
-      const c10::StorageImpl* sti = nullptr;
-      for (Py_ssize_t t = 0; t < T; ++t) {
-        PyObject* o = PyList_GET_ITEM(lst, t);
-        if (!is_tensor(o)) Py_RETURN_NONE;
-        const at::Tensor& x = THPVariable_Unpack(o);
-        if (x.dim() != 1 || x.scalar_type() != dt || x.stride(0) != 1 || x.requires_grad())
+  const at::Tensor& status = THPVariable_Unpack(a[3]);
+  // the rows: [B] tensors, one storage per list, a uniform stride between steps
+  int64_t b = -1, rs[2] = {0, 0};
+  const void* base[2] = {nullptr, nullptr};
+  c10::Device dev{c10::DeviceType::CPU};
+  for (int li = 0; li < 2; ++li) {
+    PyObject* lst = li == 0 ? al : ll_;
+    const at::ScalarType dt = li == 0 ? at::kLong : at::kFloat;
+    const int64_t esz = li == 0 ? 8 : 4;
+    const c10::StorageImpl* sti = nullptr;
+    for (Py_ssize_t t = 0; t < T; ++t) {
+      PyObject* o = PyList_GET_ITEM(lst, t);
+      if (!is_tensor(o)) Py_RETURN_NONE;
+      const at::Tensor& x = THPVariable_Unpack(o);
+      if (x.dim() != 1 || x.scalar_type() != dt || x.stride(0) != 1 || x.requires_grad())
+        Py_RETURN_NONE;
+      if (t == 0 && li == 0) {
+        dev = x.device();
+        b = x.size(0);
+        if (!dev.is_cuda() || b < 1) Py_RETURN_NONE;
+      }
+      if (x.device() != dev || x.size(0) != b) Py_RETURN_NONE;
+      const char* p = static_cast<const char*>(x.const_data_ptr());
+      if (t == 0) {
+        base[li] = p;
+        sti = x.storage().unsafeGetStorageImpl();
+      } else {
+        if (x.storage().unsafeGetStorageImpl() != sti) Py_RETURN_NONE;
+        const int64_t d = p - static_cast<const char*>(base[li]);
+        if (t == 1) {
+          if (d <= 0 || d % esz != 0 || d / esz < b) Py_RETURN_NONE;
+          rs[li] = d / esz;
+        } else if (d != (int64_t)t * rs[li] * esz) {
           Py_RETURN_NONE;
-        if (t == 0 && li == 0) {
-          dev = x.device();
-          b = x.size(0);
-          if (!dev.is_cuda() || b < 1) Py_RETURN_NONE;
-        }
-        if (x.device() != dev || x.size(0) != b) Py_RETURN_NONE;
-        const char* p = static_cast<const char*>(x.const_data_ptr());
-        if (t == 0) {
-          base[li] = p;
-          sti = x.storage().unsafeGetStorageImpl();
-        } else {
-          if (x.storage().unsafeGetStorageImpl() != sti) Py_RETURN_NONE;
-          const int64_t d = p - static_cast<const char*>(base[li]);
-          if (t == 1) {
-            if (d <= 0 || d % esz != 0 || d / esz < b) Py_RETURN_NONE;
-            rs[li] = d / esz;
-          } else if (d != (int64_t)t * rs[li] * esz) {
-            Py_RETURN_NONE;
-          }
         }
       }
-      if (T == 1) rs[li] = b;
     }
-    if (status.device() != dev || status.scalar_type() != at::kInt) Py_RETURN_NONE;
-    // the three outputs carved from one storage (one allocation instead of three)
-    Carver cv;
-    const int64_t oa = cv.take(8 * b * (int64_t)T), ol = cv.take(4 * b * (int64_t)T),
-                  os = cv.take(4 * b);
-    const c10::Storage ost = new_storage(dev, cv.off);
-    at::Tensor acts = view_of(ost, at::kLong, oa, {b, (int64_t)T});
-    at::Tensor lps = view_of(ost, at::kFloat, ol, {b, (int64_t)T});
-    at::Tensor ll;
-    if (want_ll) ll = view_of(ost, at::kFloat, os, {b});
-    void* stream = current_stream(dev);
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = fn(b, (int64_t)T, static_cast<const int64_t*>(base[0]), rs[0],
-            static_cast<const float*>(base[1]), rs[1], acts.mutable_data_ptr<int64_t>(),
-            lps.mutable_data_ptr<float>(), want_ll ? ll.mutable_data_ptr<float>() : nullptr,
-            status.mutable_data_ptr<int32_t>(), stream);
-    Py_END_ALLOW_THREADS
-    if (rc != CO_OK) return PyLong_FromLong(rc);
-    return wrap_all({&acts, &lps, &ll});
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
-    return nullptr;
+    if (T == 1) rs[li] = b;
   }
+  if (status.device() != dev || status.scalar_type() != at::kInt) Py_RETURN_NONE;
+  // the three outputs carved from one storage (one allocation instead of three)
+  Carver cv;
+  const int64_t oa = cv.take(8 * b * (int64_t)T), ol = cv.take(4 * b * (int64_t)T),
+                os = cv.take(4 * b);
+  const c10::Storage ost = new_storage(dev, cv.off);
+  at::Tensor acts = view_of(ost, at::kLong, oa, {b, (int64_t)T});
+  at::Tensor lps = view_of(ost, at::kFloat, ol, {b, (int64_t)T});
+  at::Tensor ll;
+  if (want_ll) ll = view_of(ost, at::kFloat, os, {b});
+  void* stream = current_stream(dev);
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = fn(b, (int64_t)T, static_cast<const int64_t*>(base[0]), rs[0],
+          static_cast<const float*>(base[1]), rs[1], acts.mutable_data_ptr<int64_t>(),
+          lps.mutable_data_ptr<float>(), want_ll ? ll.mutable_data_ptr<float>() : nullptr,
+          status.mutable_data_ptr<int32_t>(), stream);
+  Py_END_ALLOW_THREADS
+  if (rc != CO_OK) return PyLong_FromLong(rc);
+  return wrap_all({&acts, &lps, &ll});
 }
 
 // slap_reset_td(fn, lb_attr, td) -> True | None | error code
@@ -998,82 +907,66 @@ PyObject* episode_stack(PyObject*, PyObject* const* a, Py_ssize_t n) {
 // dict-backed TensorDict in one co_slap_reset launch: mask / to_choose / i / reward /
 // ratio / done / terminated carved from one storage and stored in the td; records i = 0,
 // the done lower bound P, and the untouched-arange record of to_choose (offset 0).
-PyObject* slap_reset_td(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 3) {
-    PyErr_SetString(PyExc_TypeError, "slap_reset_td: 3 arguments");
-    return nullptr;
-  }
+PyObject* slap_reset_td(PyObject* const* a) {
   PyObject *lb_attr = a[1], *td = a[2];
   if (!PyDict_Check(td) || !PyUnicode_Check(lb_attr)) Py_RETURN_NONE;
   PyObject *as_o = td_tensor(td, "assignment"), *fr_o = td_tensor(td, "freq"),
            *lo_o = td_tensor(td, "locs"), *dd_o = td_tensor(td, "depot_loc_dist");
   if (!as_o || !fr_o || !lo_o || !dd_o) Py_RETURN_NONE;
   const auto fn = fn_at<SlapReset>(a[0]);
-  try {
-    const at::Tensor& asg = THPVariable_Unpack(as_o);
-    const at::Tensor& fr = THPVariable_Unpack(fr_o);
-    const at::Tensor& lo = THPVariable_Unpack(lo_o);
-    const at::Tensor& dd = THPVariable_Unpack(dd_o);
-    const c10::Device dev = asg.device();
-    if (!dev.is_cuda() || asg.dim() < 1 || fr.dim() < 2 || lo.dim() < 2 || dd.dim() != 2)
-      Py_RETURN_NONE;
-    const int64_t b = asg.size(0), p = fr.size(fr.dim() - 2), l = lo.size(1);
-    if (dd.size(0) != b || dd.size(1) != l) Py_RETURN_NONE;
-    Carver c;
-    const int64_t om = c.take(b * l), ot = c.take(4 * b * p), oi = c.take(8 * b),
-                  orw = c.take(4 * b), ora = c.take(4 * b * l), od = c.take(b), oe = c.take(b);
-    c10::Storage st = new_storage(dev, c.off);
-    at::Tensor mask = view_of(st, at::kBool, om, {b, l});
-    at::Tensor tc = view_of(st, at::kFloat, ot, {b, p});
-    at::Tensor it = view_of(st, at::kLong, oi, {b, 1});
-    at::Tensor rw = view_of(st, at::kFloat, orw, {b, 1});
-    at::Tensor ratio = view_of(st, at::kFloat, ora, {b, l});
-    at::Tensor done = view_of(st, at::kBool, od, {b, 1});
-    at::Tensor term = view_of(st, at::kBool, oe, {b, 1});
-    void* stream = current_stream(dev);
-    g_slap_stream = stream;  // the episode's tensors are made in this stream's order
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = fn(b, l, p, static_cast<uint8_t*>(mask.mutable_data_ptr()), tc.mutable_data_ptr<float>(),
-            it.mutable_data_ptr<int64_t>(), rw.mutable_data_ptr<float>(),
-            ratio.mutable_data_ptr<float>(), static_cast<uint8_t*>(done.mutable_data_ptr()),
-            static_cast<uint8_t*>(term.mutable_data_ptr()), stream);
-    Py_END_ALLOW_THREADS
-    if (rc != CO_OK) return PyLong_FromLong(rc);
-    std::pair<const char*, at::Tensor*> outs[] = {
-        {"to_choose", &tc}, {"i", &it},       {"ratio", &ratio},   {"action_mask", &mask},
-        {"reward", &rw},    {"done", &done}, {"terminated", &term}};
-    for (auto& kv : outs) {
-      PyObject* o = THPVariable_Wrap(std::move(*kv.second));
-      if (!o) return nullptr;
-      int err = 0;
-      if (kv.first[0] == 'i') err = remember(o, g_attr_i, 0) || remember(o, lb_attr, p);
-      else if (kv.first[0] == 't' && kv.first[1] == 'o') err = remember(o, g_attr_tc, 0);
-      if (!err) err = PyDict_SetItem(td, key_of(kv.first), o);
-      Py_DECREF(o);
-      if (err) return nullptr;
-    }
-    Py_RETURN_TRUE;
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
+  const at::Tensor& asg = THPVariable_Unpack(as_o);
+  const at::Tensor& fr = THPVariable_Unpack(fr_o);
+  const at::Tensor& lo = THPVariable_Unpack(lo_o);
+  const at::Tensor& dd = THPVariable_Unpack(dd_o);
+  const c10::Device dev = asg.device();
+  if (!dev.is_cuda() || asg.dim() < 1 || fr.dim() < 2 || lo.dim() < 2 || dd.dim() != 2)
+    Py_RETURN_NONE;
+  const int64_t b = asg.size(0), p = fr.size(fr.dim() - 2), l = lo.size(1);
+  if (dd.size(0) != b || dd.size(1) != l) Py_RETURN_NONE;
+  Carver c;
+  const int64_t om = c.take(b * l), ot = c.take(4 * b * p), oi = c.take(8 * b),
+                orw = c.take(4 * b), ora = c.take(4 * b * l), od = c.take(b), oe = c.take(b);
+  c10::Storage st = new_storage(dev, c.off);
+  at::Tensor mask = view_of(st, at::kBool, om, {b, l});
+  at::Tensor tc = view_of(st, at::kFloat, ot, {b, p});
+  at::Tensor it = view_of(st, at::kLong, oi, {b, 1});
+  at::Tensor rw = view_of(st, at::kFloat, orw, {b, 1});
+  at::Tensor ratio = view_of(st, at::kFloat, ora, {b, l});
+  at::Tensor done = view_of(st, at::kBool, od, {b, 1});
+  at::Tensor term = view_of(st, at::kBool, oe, {b, 1});
+  void* stream = current_stream(dev);
+  g_slap_stream = stream;  // the episode's tensors are made in this stream's order
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = fn(b, l, p, static_cast<uint8_t*>(mask.mutable_data_ptr()), tc.mutable_data_ptr<float>(),
+          it.mutable_data_ptr<int64_t>(), rw.mutable_data_ptr<float>(),
+          ratio.mutable_data_ptr<float>(), static_cast<uint8_t*>(done.mutable_data_ptr()),
+          static_cast<uint8_t*>(term.mutable_data_ptr()), stream);
+  Py_END_ALLOW_THREADS
+  if (rc != CO_OK) return PyLong_FromLong(rc);
+  const TdEntry outs[] = {{"to_choose", &tc}, {"i", &it},      {"ratio", &ratio},
+                          {"action_mask", &mask}, {"reward", &rw}, {"done", &done},
+                          {"terminated", &term}};
+  for (const TdEntry& e : outs)
+    if (set_wrapped(td, e.key, *e.fresh)) return nullptr;
+  PyObject* i_n = PyDict_GetItem(td, key_of("i"));  // borrowed: what the td now holds
+  PyObject* tc_n = PyDict_GetItem(td, key_of("to_choose"));
+  if (!i_n || !tc_n || remember(i_n, g_attr_i, 0) || remember(i_n, lb_attr, p) ||
+      remember(tc_n, g_attr_tc, 0))
     return nullptr;
-  }
+  Py_RETURN_TRUE;
 }
 
 // set_inplace(flag) -> previous flag: allow the in-place state writes (only where the
 // build allows them: kInplaceBuild); inplace_policy() -> (build allows, enabled)
-PyObject* set_inplace(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 1) {
-    PyErr_SetString(PyExc_TypeError, "set_inplace: 1 argument");
-    return nullptr;
-  }
+PyObject* set_inplace(PyObject* const* a) {
   const int v = PyObject_IsTrue(a[0]);
   if (v < 0) return nullptr;
   const bool prev = g_inplace;
   g_inplace = kInplaceBuild && v;
   return PyBool_FromLong(prev);
 }
-PyObject* inplace_policy(PyObject*, PyObject* const*, Py_ssize_t) {
+PyObject* inplace_policy(PyObject* const*) {
   return Py_BuildValue("(OO)", kInplaceBuild ? Py_True : Py_False, g_inplace ? Py_True : Py_False);
 }
 
@@ -1087,11 +980,7 @@ PyObject* inplace_policy(PyObject*, PyObject* const*, Py_ssize_t) {
 // False and whose int status goes to check_rc("decode_and_step", rc); then
 // strategy.<idx_attr> += 1 and the (action, logp) pair appended to the two lists.  The
 // same calls in the same order as the Python closure, without its frame per step.
-PyObject* fast_step(PyObject*, PyObject* const* a, Py_ssize_t n) {
-  if (n != 15) {
-    PyErr_SetString(PyExc_TypeError, "fast_step: 15 arguments");
-    return nullptr;
-  }
+PyObject* fast_step(PyObject* const* a) {
   PyObject *td = a[12], *logits = a[13], *mask = a[14];
   if (reinterpret_cast<PyObject*>(Py_TYPE(td)) != a[1] || !PyDict_Check(td) ||
       PyDict_GetItem(td, key_of("action_mask")) != mask)
@@ -1151,42 +1040,68 @@ PyObject* fast_step(PyObject*, PyObject* const* a, Py_ssize_t n) {
 }
 
 // clear_pool() -> None: drop every pooled state storage (tensors still held stay valid)
-PyObject* clear_pool(PyObject*, PyObject* const*, Py_ssize_t) {
+PyObject* clear_pool(PyObject* const*) {
   g_state.clear();
   Py_RETURN_NONE;
 }
 
+// The METH_FASTCALL entry of an implementation `PyObject* f(PyObject* const* args)`: the
+// arity check (TypeError "<name>: K arguments"; arity < 0: any) and the guard that turns a
+// std::exception (an ATen / allocator error) into RuntimeError.
+using Impl = PyObject* (*)(PyObject* const*);
+using FastCall = PyObject* (*)(PyObject*, PyObject* const*, Py_ssize_t);
+
+template <Impl F>
+PyObject* entry(PyObject* const* a, Py_ssize_t n, Py_ssize_t arity, const char* arity_msg) {
+  if (arity >= 0 && n != arity) {
+    PyErr_SetString(PyExc_TypeError, arity_msg);
+    return nullptr;
+  }
+  try {
+    return F(a);
+  } catch (const std::exception& e) {
+    PyErr_SetString(PyExc_RuntimeError, e.what());
+    return nullptr;
+  }
+}
+
+inline PyMethodDef method(const char* name, FastCall f, const char* doc) {
+  return {name, reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(f)), METH_FASTCALL,
+          doc};
+}
+
+#define CO_METHOD(f, arity, noun, doc)                                        \
+  method(#f,                                                                  \
+         [](PyObject*, PyObject* const* a, Py_ssize_t n) -> PyObject* {       \
+           return entry<f>(a, n, arity, #f ": " #arity " " noun);             \
+         },                                                                   \
+         doc)
+
 PyMethodDef methods[] = {
-    {"slap_step_td", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(slap_step_td)),
-     METH_FASTCALL, "SLAPEnv.decode_and_step on a dict-backed TensorDict, in one call"},
-    {"cvrp_step_td", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(cvrp_step_td)),
-     METH_FASTCALL, "CVRPEnv.decode_and_step on a dict-backed TensorDict, in one call"},
-    {"set_inplace", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(set_inplace)),
-     METH_FASTCALL, "allow / forbid the in-place state writes; returns the previous flag"},
-    {"inplace_policy",
-     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(inplace_policy)),
-     METH_FASTCALL, "(build allows in-place writes, enabled)"},
-    {"fast_step", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(fast_step)),
-     METH_FASTCALL, "the greedy decode loop's per-step closure (fast_stepper) in C"},
-    {"clear_pool", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(clear_pool)),
-     METH_FASTCALL, "drop the pooled step-state storages"},
-    {"slab_fresh", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(slab_fresh)),
-     METH_FASTCALL, "start a new action / log-probability slab at the next step"},
-    {"episode_stack",
-     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(episode_stack)),
-     METH_FASTCALL, "the decode loop's stack + log-likelihood epilogue in one launch"},
-    {"slap_reset_td",
-     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(slap_reset_td)),
-     METH_FASTCALL, "SLAPEnv._reset + the reset's done / terminated in one launch"},
-    {"tsp_step_td", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(tsp_step_td)),
-     METH_FASTCALL, "TSPEnv.decode_and_step on a dict-backed TensorDict, in one call"},
-    {"decode_step", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(decode_step)),
-     METH_FASTCALL, "decode step: outputs allocated and launched in one call"},
-    {"cvrp_step", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(cvrp_step)),
-     METH_FASTCALL, "CVRP env step: outputs allocated and launched in one call"},
-    {"tsp_decode_step",
-     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(tsp_decode_step)),
-     METH_FASTCALL, "fused TSP decode step: outputs allocated and launched in one call"},
+    CO_METHOD(slap_step_td, 12, "arguments",
+              "SLAPEnv.decode_and_step on a dict-backed TensorDict, in one call"),
+    CO_METHOD(cvrp_step_td, 12, "arguments",
+              "CVRPEnv.decode_and_step on a dict-backed TensorDict, in one call"),
+    CO_METHOD(set_inplace, 1, "argument",
+              "allow / forbid the in-place state writes; returns the previous flag"),
+    CO_METHOD(inplace_policy, -1, "", "(build allows in-place writes, enabled)"),
+    CO_METHOD(fast_step, 15, "arguments",
+              "the greedy decode loop's per-step closure (fast_stepper) in C"),
+    CO_METHOD(clear_pool, -1, "", "drop the pooled step-state storages"),
+    CO_METHOD(slab_fresh, 1, "argument",
+              "start a new action / log-probability slab at the next step"),
+    CO_METHOD(episode_stack, 5, "arguments",
+              "the decode loop's stack + log-likelihood epilogue in one launch"),
+    CO_METHOD(slap_reset_td, 3, "arguments",
+              "SLAPEnv._reset + the reset's done / terminated in one launch"),
+    CO_METHOD(tsp_step_td, 12, "arguments",
+              "TSPEnv.decode_and_step on a dict-backed TensorDict, in one call"),
+    CO_METHOD(decode_step, 11, "arguments",
+              "decode step: outputs allocated and launched in one call"),
+    CO_METHOD(cvrp_step, 6, "arguments",
+              "CVRP env step: outputs allocated and launched in one call"),
+    CO_METHOD(tsp_decode_step, 13, "arguments",
+              "fused TSP decode step: outputs allocated and launched in one call"),
     {nullptr, nullptr, 0, nullptr}};
 
 PyModuleDef module = {PyModuleDef_HEAD_INIT, "_co_torchstep",

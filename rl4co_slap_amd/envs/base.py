@@ -18,6 +18,7 @@ Differences from the reference, all deliberate:
 from __future__ import annotations
 
 import abc
+import functools
 import os
 from typing import Iterable, Optional
 
@@ -221,12 +222,7 @@ class RL4COEnvBase(metaclass=abc.ABCMeta):
         if self._checks is not None and self._checks.owns(status):
             self._checks.add(messages)
             return
-        d = nat.pending_deferred(status.device) if status.device.type != "cpu" else None
-        if d is not None:
-            bits, dbits = (int(v) for v in torch.cat([status.reshape(1), d]).tolist())
-            nat.raise_deferred(dbits, status.device)
-        else:
-            bits = int(status.item())
+        bits, = nat.read_status([status], status.device)
         nat.release_status(status, (bits,))
         for bit, exc, msg in messages:
             if bits & bit:
@@ -259,6 +255,38 @@ class RL4COEnvBase(metaclass=abc.ABCMeta):
         d.pop("_co_i", None)
         d.pop(self._lb_attr, None)
         return t
+
+    # -- the fused decode + env step (an env's decode_and_step) -----------------------
+    def _bound_glue(self, attr):
+        """An env's ``native_decode_and_step``: the step glue's ``attr``
+        (``csrc/pycall/co_torchstep.cpp``) as ``f(td, logits, mode, temperature,
+        tanh_clipping, action_in, seed, offset, status, key)`` returning ``(action, logp)``,
+        an error code, or None (then call ``decode_and_step``); None without the glue."""
+        ts = nat.torchstep()
+        return None if ts is None else functools.partial(getattr(ts, attr), self._lb_attr)
+
+    @staticmethod
+    def _fused_operands(logits, action_in, state, extra_cols: int = 0):
+        """What the envs' Python ``decode_and_step`` share.  ``state`` is the 2-D state
+        tensor ``[b, n]`` the logits rows pair with (``n + extra_cols`` columns).  None
+        when the fused kernels do not take the logits (not f32 ``[b, n + extra_cols]`` with
+        a unit inner stride on ``state``'s CUDA device, or rows past the register row
+        engines); else ``(b, n, action_in as contiguous int64, act, logp, sel, stream)``:
+        ``act`` / ``logp`` the un-pooled outputs (the decoding strategy keeps every step's)
+        and ``sel`` the action the td stores (``action_in`` when given, else ``act``)."""
+        dev = logits.device
+        if dev.type != "cuda" or state.device != dev:
+            return None
+        if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(-1) != 1:
+            return None
+        b, n = state.shape
+        if logits.shape != (b, n + extra_cols) or n + extra_cols > 2048:
+            return None
+        ain = action_in.long().contiguous() if action_in is not None else None
+        act = torch.empty(b, dtype=torch.int64, device=dev)
+        logp = torch.empty(b, dtype=torch.float32, device=dev)
+        return (b, n, ain, act, logp, action_in if action_in is not None else act,
+                nat.stream_of(logits))
 
     # -- done-poll lower bounds ---------------------------------------------------
     def _remember_lb(self, t: torch.Tensor, steps: int):

@@ -116,10 +116,9 @@ class CVRPEnv(RL4COEnvBase):
         demand, used, vcap, visited = (td["demand"], td["used_capacity"], td["vehicle_capacity"],
                                        td["visited"])
         ts = nat.torchstep()
-        r = ts.cvrp_step(action, demand, used, vcap, visited) if ts is not None else None
+        r = nat.glue_result("co_cvrp_step", ts.cvrp_step(action, demand, used, vcap, visited)) \
+            if ts is not None else None
         if r is not None:  # output allocation + launch in one native call
-            if type(r) is int:
-                nat.check_rc("co_cvrp_step", r)
             used_out, visited_out, cur, done, reward, mask = r
             return self._after_step(td, used_out, visited_out, cur, done, reward, mask)
         nat.require_device(action, demand, used, vcap, visited)
@@ -150,17 +149,9 @@ class CVRPEnv(RL4COEnvBase):
         return td
 
     def native_decode_and_step(self):
-        """``decode_and_step``'s native call for a decoding strategy's loop (the step glue
-        ``csrc/pycall/co_torchstep.cpp``: cvrp_step_td): ``f(td, logits, mode, temperature,
-        tanh_clipping, action_in, seed, offset, status, key)`` returning ``(action, logp)``,
-        an error code, or None (then call ``decode_and_step``); None when the glue is
-        unavailable."""
-        ts = nat.torchstep()
-        if ts is None:
-            return None
-        import functools
-
-        return functools.partial(ts.cvrp_step_td, self._lb_attr)
+        """``decode_and_step`` in one native call (``cvrp_step_td``), which a decoding
+        strategy's loop tries first: see ``_bound_glue``."""
+        return self._bound_glue("cvrp_step_td")
 
     def decode_and_step(self, td, logits, mode, temperature, tanh_clipping, action_in, seed,
                         offset, status, key="action"):
@@ -173,21 +164,18 @@ class CVRPEnv(RL4COEnvBase):
                                              td["used_capacity"], td["vehicle_capacity"],
                                              td["visited"])
         dev = logits.device
-        if dev.type != "cuda" or any(x.device != dev for x in (mask, demand, used, vcap, visited)):
+        if any(x.device != dev for x in (mask, used, vcap, visited)):
             return None
-        if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(-1) != 1:
+        ops = self._fused_operands(logits, action_in, demand, extra_cols=1)
+        if ops is None:
             return None
-        b, n = demand.shape
-        if (logits.shape != (b, n + 1) or mask.shape != (b, n + 1) or n + 1 > 2048
+        b, n, ain, act, logp, sel, s = ops
+        if (mask.shape != (b, n + 1)
                 or visited.dtype != torch.uint8 or demand.dtype != torch.float32
                 or used.dtype != torch.float32 or vcap.dtype != torch.float32
                 or used.numel() != b or vcap.numel() != b):
             return None
         m, demand, used, vcap, visited = (x.contiguous() for x in (mask, demand, used, vcap, visited))
-        ain = action_in.long().contiguous() if action_in is not None else None
-        s = nat.stream_of(m)
-        act = torch.empty(b, dtype=torch.int64, device=dev)  # kept by the strategy
-        logp = torch.empty(b, dtype=torch.float32, device=dev)
         used_out = self._out(used.shape, used.dtype, dev, s)
         visited_out = self._out(visited.shape, visited.dtype, dev, s)
         cur = self._out((b, 1), torch.int64, dev, s)
@@ -199,7 +187,6 @@ class CVRPEnv(RL4COEnvBase):
                  nat.ptr(logp), seed, offset, nat.ptr(demand), nat.ptr(used), nat.ptr(used_out),
                  nat.ptr(vcap), nat.ptr(visited), nat.ptr(visited_out), nat.ptr(cur),
                  nat.ptr(done), nat.ptr(reward), nat.ptr(mask_out), None, nat.ptr(status), s)
-        sel = action_in if action_in is not None else act
         set_many(td, {key: sel})
         self._after_step(td, used_out, visited_out, cur, done, reward, mask_out)
         return sel, logp

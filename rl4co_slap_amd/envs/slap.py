@@ -122,10 +122,7 @@ class SLAPEnv(RL4COEnvBase):
         outputs, set straight into ``td``)."""
         ts = nat.torchstep() if type(td) is TensorDict else None
         if ts is not None:
-            r = ts.slap_reset_td(self._lb_attr, td)
-            if type(r) is int:
-                nat.check_rc("co_slap_reset", r)
-            if r is not None:
+            if nat.glue_result("co_slap_reset", ts.slap_reset_td(self._lb_attr, td)) is not None:
                 return td
         assignment = td["assignment"]
         nat.require_device(assignment)
@@ -197,17 +194,9 @@ class SLAPEnv(RL4COEnvBase):
         return super().poll_done(td)
 
     def native_decode_and_step(self):
-        """``decode_and_step``'s native call for a decoding strategy's loop (the step glue
-        ``csrc/pycall/co_torchstep.cpp``: slap_step_td): ``f(td, logits, mode, temperature,
-        tanh_clipping, action_in, seed, offset, status, key)`` returning ``(action, logp)``,
-        an error code, or None (then call ``decode_and_step``); None when the glue is
-        unavailable."""
-        ts = nat.torchstep()
-        if ts is None:
-            return None
-        import functools
-
-        return functools.partial(ts.slap_step_td, self._lb_attr)
+        """``decode_and_step`` in one native call (``slap_step_td``), which a decoding
+        strategy's loop tries first: see ``_bound_glue``."""
+        return self._bound_glue("slap_step_td")
 
     def decode_and_step(self, td, logits, mode, temperature, tanh_clipping, action_in, seed,
                         offset, status, key="action"):
@@ -219,13 +208,14 @@ class SLAPEnv(RL4COEnvBase):
         tensors, non-f32 logits, rows past the register row engines, no product left)."""
         mask, i, tc, assign = td["action_mask"], td["i"], td["to_choose"], td["assignment"]
         dev = logits.device
-        if dev.type != "cuda" or any(x.device != dev for x in (mask, i, tc, assign)):
+        if any(x.device != dev for x in (i, tc, assign)):
             return None
-        if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(-1) != 1:
+        ops = self._fused_operands(logits, action_in, mask)
+        if ops is None:
             return None
-        b, l = mask.shape
-        if (logits.shape != (b, l) or l > 2048 or assign.dtype != torch.int32 or tc.dim() != 2
-                or tc.shape[-1] == 0 or tc.dtype != torch.float32):
+        b, l, ain, act, logp, sel, s = ops
+        if (assign.dtype != torch.int32 or tc.dim() != 2 or tc.shape[-1] == 0
+                or tc.dtype != torch.float32):
             return None
         p = td["freq"].shape[-2]
         # the operands the kernel indexes: i [b] int64, assignment [b, P] (it writes r*P + c)
@@ -235,11 +225,6 @@ class SLAPEnv(RL4COEnvBase):
         if action_in is not None and action_in.numel() != b:
             return None
         m, i, assign = mask.contiguous(), i.contiguous(), assign.contiguous()
-        ain = action_in.long().contiguous() if action_in is not None else None
-        s = nat.stream_of(m)
-        # the decoding strategy keeps every action and log-probability: never pooled
-        act = torch.empty(b, dtype=torch.int64, device=dev)
-        logp = torch.empty(b, dtype=torch.float32, device=dev)
         assign_out = self._out(assign.shape, assign.dtype, dev, s)
         mask_out = self._out(m.shape, m.dtype, dev, s)
         i_out = self._out(i.shape, i.dtype, dev, s)
@@ -251,7 +236,6 @@ class SLAPEnv(RL4COEnvBase):
                  nat.ptr(assign_out), nat.ptr(mask_out), nat.ptr(i), nat.ptr(i_out),
                  nat.ptr(done), nat.ptr(reward), None, nat.ptr(status), s)
         self._step_records(td["i"], i_out, done, p)
-        sel = action_in if action_in is not None else act
         set_many(td, {key: sel, "assignment": assign_out, "to_choose": tc[..., 1:],
                       "action_mask": mask_out, "i": i_out, "reward": reward, "done": done})
         return sel, logp

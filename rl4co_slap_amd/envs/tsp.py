@@ -101,6 +101,11 @@ class TSPEnv(RL4COEnvBase):
                    "action_mask": mask_out, "reward": reward, "done": done})
         return td
 
+    def native_decode_and_step(self):
+        """``decode_and_step`` in one native call (``tsp_step_td``, bookkeeping included),
+        which a decoding strategy's loop tries first: see ``_bound_glue``."""
+        return self._bound_glue("tsp_step_td")
+
     def decode_and_step(self, td, logits, mode, temperature, tanh_clipping, action_in, seed,
                         offset, status, key="action"):
         """``DecodingStrategy.step`` + ``_step`` (``decoding.py:327-369``, ``tsp/env.py:67-93``)
@@ -108,31 +113,6 @@ class TSPEnv(RL4COEnvBase):
         and aliasing (``current_node`` is the action tensor) as the two calls.  Returns
         ``(action, logp)``, or None when it does not apply (CPU tensors, unknown ``i``
         provenance for the batch-wide first-node test, non-f32 logits)."""
-        ts = nat.torchstep()
-        if ts is not None:  # the whole step, bookkeeping included, in one native call
-            r = ts.tsp_step_td(self._lb_attr, td, logits, mode, temperature, tanh_clipping,
-                               action_in, seed, offset, status, key)
-            if r is not None:
-                if type(r) is int:
-                    nat.check_rc("co_tsp_decode_step", r)
-                return r
-        return self._decode_and_step_py(td, logits, mode, temperature, tanh_clipping,
-                                        action_in, seed, offset, status, key)
-
-    def native_decode_and_step(self):
-        """``decode_and_step``'s native call for a decoding strategy's loop: ``f(td,
-        logits, mode, temperature, tanh_clipping, action_in, seed, offset, status, key)``
-        returning ``(action, logp)``, an error code, or None (then call
-        ``decode_and_step``); None when the step glue is unavailable."""
-        ts = nat.torchstep()
-        if ts is None:
-            return None
-        import functools
-
-        return functools.partial(ts.tsp_step_td, self._lb_attr)
-
-    def _decode_and_step_py(self, td, logits, mode, temperature, tanh_clipping, action_in,
-                            seed, offset, status, key):
         mask, i = td["action_mask"], td["i"]
         known = self._known_i(i)
         if known is None:
@@ -143,30 +123,21 @@ class TSPEnv(RL4COEnvBase):
             return None
         ts = nat.torchstep()
         if ts is not None:  # output allocation + launch in one native call
-            r = ts.tsp_decode_step(logits, mask, i, None if take else first_in, action_in,
-                                   status, float(tanh_clipping), float(temperature), mode, seed,
-                                   offset, take)
+            r = nat.glue_result("co_tsp_decode_step", ts.tsp_decode_step(
+                logits, mask, i, None if take else first_in, action_in, status,
+                float(tanh_clipping), float(temperature), mode, seed, offset, take))
             if r is not None:
-                if type(r) is int:
-                    nat.check_rc("co_tsp_decode_step", r)
                 act, logp, mask_out, i_out, first_out, done, reward = r
-                return self._after_decode_step(td, key, action_in, act, logp, mask, mask_out,
-                                               i_out, first_out, done, reward, known)
-        if logits.device.type != "cuda" or mask.device != logits.device:
+                return self._after_decode_step(td, key, act if action_in is None else action_in,
+                                               logp, mask, mask_out, i_out, first_out, done,
+                                               reward, known)
+        ops = self._fused_operands(logits, action_in, mask)
+        if ops is None:
             return None
-        if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(-1) != 1:
-            return None
-        b, n = mask.shape
-        if logits.shape != (b, n) or n > 2048:  # long rows: co_decode_step's row kernel
-            return None
+        b, n, ain, act, logp, sel, s = ops
         dev = mask.device
         m, i = mask.contiguous(), i.contiguous()
         first_in = first_in.contiguous() if (first_in is not None and not take) else None
-        ain = action_in.long().contiguous() if action_in is not None else None
-        s = nat.stream_of(m)
-        # the decoding strategy keeps every action and log-probability: never pooled
-        act = torch.empty(b, dtype=torch.int64, device=dev)
-        logp = torch.empty(b, dtype=torch.float32, device=dev)
         mask_out = self._out(m.shape, m.dtype, dev, s)
         i_out = self._out(i.shape, i.dtype, dev, s)
         first_out = self._out((b,), torch.int64, dev, s)
@@ -177,12 +148,11 @@ class TSPEnv(RL4COEnvBase):
                  nat.ptr(logp), seed, offset, nat.ptr(mask_out), nat.ptr(i), nat.ptr(i_out),
                  nat.ptr(first_in), nat.ptr(first_out), take, nat.ptr(done), nat.ptr(reward),
                  None, nat.ptr(status), s)
-        return self._after_decode_step(td, key, action_in, act, logp, mask, mask_out, i_out,
-                                       first_out, done, reward, known)
+        return self._after_decode_step(td, key, sel, logp, mask, mask_out, i_out, first_out,
+                                       done, reward, known)
 
-    def _after_decode_step(self, td, key, action_in, act, logp, mask, mask_out, i_out,
-                           first_out, done, reward, known):
-        sel = action_in if action_in is not None else act
+    def _after_decode_step(self, td, key, sel, logp, mask, mask_out, i_out, first_out, done,
+                           reward, known):
         self._remember_i(i_out, known + 1)
         lb = self._known_lb(mask)
         if lb is not None:

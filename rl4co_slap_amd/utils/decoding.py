@@ -63,11 +63,10 @@ def decode_step(logits, mask, mode: str, temperature=1.0, tanh_clipping=0.0, act
         seed = int(torch.randint(0, 2**62, ()).item()) if mode == "sampling" else 0
     ts = nat.torchstep() if top_k <= 0 and top_p <= 0 else None
     if ts is not None:  # output allocation + launch in one native call (device tensors)
-        r = ts.decode_step(logits, mask, action, status, float(tanh_clipping),
-                           float(temperature), mword, seed, offset, return_full)
+        r = nat.glue_result("co_decode_step", ts.decode_step(
+            logits, mask, action, status, float(tanh_clipping), float(temperature), mword, seed,
+            offset, return_full))
         if r is not None:
-            if type(r) is int:
-                nat.check_rc("co_decode_step", r)
             return r
     nat.require_device(logits, mask, action)
     if logits.dtype != torch.float32:
@@ -234,10 +233,7 @@ class _Checks:
         """-> the decode word's bits (the caller raises / records them); raises the env
         messages and the device's deferred gather errors."""
         st = self.status
-        d = nat.pending_deferred(st.device) if st.device.type != "cpu" else None
-        vals = [int(v) for v in (torch.cat([st, d]) if d is not None else st).tolist()]
-        if d is not None:
-            nat.raise_deferred(vals[2], st.device)
+        vals = nat.read_status([st], st.device)
         w0, w1 = vals[0], vals[1]
         if w0 & nat.ST_INFEASIBLE:
             raise AssertionError("infeasible action selected")
@@ -320,9 +316,8 @@ class DecodingStrategy(metaclass=abc.ABCMeta):
         if (st is not None and st.device.type != "cpu" and st.shape[0] >= 2
                 and not self.store_all_logp):
             ts = nat.torchstep()
-            r = ts.episode_stack(self.actions, self.logprobs, st, True) if ts is not None else None
-            if type(r) is int:
-                nat.check_rc("co_episode_stack", r)
+            r = nat.glue_result("co_episode_stack", ts.episode_stack(
+                self.actions, self.logprobs, st, True)) if ts is not None else None
             if r is None:
                 r = _stack_device(self.actions, self.logprobs, st)
         if r is not None:
@@ -349,14 +344,8 @@ class DecodingStrategy(metaclass=abc.ABCMeta):
                                                                 device=logprobs.device))
         ok = ok.to(torch.int32)
         st = self._status[0] if self._status is not None else torch.zeros_like(ok)
-        words = [st.reshape(()), ok]
-        d = nat.pending_deferred(ok.device) if ok.device.type != "cpu" else None
-        if d is not None:  # an out-of-range gather_by_index since the last read
-            words.append(d.reshape(()))
-        vals = [int(v) for v in torch.stack(words).tolist()]
-        st_bits, lp_ok = vals[0], vals[1]
-        if d is not None:
-            nat.raise_deferred(vals[2], ok.device)
+        # (with the device's deferred word: an out-of-range gather_by_index since the last read)
+        st_bits, lp_ok = nat.read_status([st, ok], ok.device)
         if st_bits & nat.ST_INFEASIBLE:
             raise AssertionError("infeasible action selected")
         if flat:
@@ -395,14 +384,19 @@ class DecodingStrategy(metaclass=abc.ABCMeta):
         of the decode loop's checks, _Checks)."""
         return nat.scratch_status(device, 2)
 
+    def _begin_step(self, device):
+        """Before a decode step's launch: the status words exist, and an episode's first
+        step starts its slab."""
+        if self._status is None:
+            self._status = self._new_status(device)
+        if self._step_idx == 0:
+            self._episode_start()
+
     def step(self, logits, mask, td: TensorDict = None, action=None, env=None, **kwargs):
         """``decoding.py:327-369`` as one fused launch."""
         if not self.mask_logits:
             mask = None
-        if self._status is None:
-            self._status = self._new_status(logits.device)
-        if self._step_idx == 0:
-            self._episode_start()
+        self._begin_step(logits.device)
         mode = self._mode()
         act_in = action if mode == "evaluate" else None
         seed = getattr(self, "_seed_carry", None)
@@ -452,18 +446,14 @@ class DecodingStrategy(metaclass=abc.ABCMeta):
         held = dict.get(td, "action_mask") if type(td) is TensorDict else td.get("action_mask")
         if mask is not held:
             return None
-        if self._status is None:
-            self._status = self._new_status(logits.device)
-        if self._step_idx == 0:
-            self._episode_start()
+        self._begin_step(logits.device)
         seed = int(torch.randint(0, 2**62, ()).item()) if mode == "sampling" else 0
         ain = action if mode == "evaluate" else None
         out = None
         if native is not None:
-            out = native(td, logits, mword, self.temperature, self.tanh_clipping, ain, seed,
-                         self._step_idx, self._status, self.key)
-            if type(out) is int:
-                nat.check_rc("decode_and_step", out)
+            out = nat.glue_result("decode_and_step", native(
+                td, logits, mword, self.temperature, self.tanh_clipping, ain, seed,
+                self._step_idx, self._status, self.key))
         if out is None:
             out = fused(td, logits, mword, self.temperature, self.tanh_clipping, ain, seed,
                         self._step_idx, self._status, self.key)
@@ -507,11 +497,10 @@ class DecodingStrategy(metaclass=abc.ABCMeta):
         def stepper(td, logits, mask):
             if type(td) is not td_type or mask is not dget(td, "action_mask"):
                 return False
-            out = native(td, logits, mword, temp, clip, None, 0, self._step_idx, st, key)
+            out = nat.glue_result("decode_and_step", native(
+                td, logits, mword, temp, clip, None, 0, self._step_idx, st, key))
             if out is None:
                 return False
-            if type(out) is int:
-                nat.check_rc("decode_and_step", out)
             self._step_idx += 1
             push_a(out[0])
             push_l(out[1])

@@ -81,7 +81,10 @@ out["env.reset"] = us(reset, 1000)
 
 def reset_step():
     t = reset()
-    return env.decode_and_step(t, logits, nat.DECODE_CERTIFIED, 1.0, 0.0, None, 0, 0, st)
+    args = (t, logits, nat.DECODE_CERTIFIED, 1.0, 0.0, None, 0, 0, st, "action")
+    native = env.native_decode_and_step()  # the glue first, as the decoding strategy does
+    r = nat.glue_result("decode_and_step", native(*args)) if native is not None else None
+    return r if r is not None else env.decode_and_step(*args)
 
 
 out["env.reset + decode_and_step"] = us(reset_step, 1000)
