@@ -22,7 +22,7 @@ SOURCES = ["tsp.hip", "cvrp.hip", "slap.hip", "ops.hip", "decode_step.hip", "dec
            "rollout.hip",
            "nearest.hip", "two_opt.hip", "cvrp_ls.hip", "slap_ls.hip"]
 HEADERS = ["co_common.hpp", "co_tile.hpp", "co_math.hpp", "co_diag.hpp", "decode_common.hpp",
-           "co_local_search.hpp"]
+           "decode_fused.hpp", "co_local_search.hpp"]
 ARCH = "gfx950"
 
 

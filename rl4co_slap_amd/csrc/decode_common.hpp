@@ -2,14 +2,17 @@
 // tanh clip -> mask to -inf -> /temperature -> log_softmax -> greedy argmax |
 // Philox inverse-CDF sample | evaluate -> logp gather, in one pass.
 //
-// RL = 16/32/64 lanes per row (several rows per wave, grid-stride); the row's logits
-// stay in registers (EPL per lane), max / sum / argmax are xor-shuffle reductions
-// inside the lane group and the sampling CDF is a group inclusive scan.  log_softmax is evaluated with the
-// same association as ATen's CPU kernel: logp = (x - max) - log(sum(exp(x - max))),
-// so greedy ties resolve exactly like torch.argmax (first index).
+// RL = 4 ... 64 lanes per row by row-length bucket (row_bucket below), 64 / RL rows per
+// wave, one row group per wave (the grid covers the batch); the row's logits stay in
+// registers (EPL per lane), max / sum / argmax are DPP / permlane reductions inside the
+// lane group and the sampling CDF is a group inclusive scan.  log_softmax is evaluated
+// with the same association as ATen's CPU kernel: logp = (x - max) - log(sum(exp(x -
+// max))), so greedy ties resolve exactly like torch.argmax (first index).
 #pragma once
-// Shared by decode_step.hip (co_decode_step[_ex], beam search) and decode_tsp.hip
-// (co_tsp_decode_step): two translation units, compiled in parallel.
+// The row engines, the plain and long-row kernels and the dispatch macros, shared by
+// decode_step.hip (co_decode_step[_ex], beam search) and, through decode_fused.hpp, by
+// decode_tsp.hip and decode_env.hip (the fused decode + env steps): three translation
+// units, compiled in parallel.
 #include "co_common.hpp"
 #include "co_diag.hpp"
 #include "co_math.hpp"
@@ -504,6 +507,23 @@ struct GreedyRow {
     }
   }
 
+  // the fused env steps' mask edits: action `a` leaves the mask (its byte cleared in the
+  // lane's words); is any action still allowed (pad slots read as masked)
+  template <class A>
+  __device__ __forceinline__ void clear(A a, int c0) {
+#pragma unroll
+    for (int j = 0; j < EPL / 4; ++j) {
+      const int off = (int)(a - (c0 + 4 * j));
+      if ((unsigned)off < 4u) mw[j] &= ~(0xffu << (8 * off));
+    }
+  }
+  __device__ __forceinline__ bool any_allowed() const {
+    uint32_t left = 0u;
+#pragma unroll
+    for (int j = 0; j < EPL / 4; ++j) left |= mw[j];
+    return left != 0u;
+  }
+
   // the row's mask words / logp values back to memory (pad chunks skipped)
   __device__ __forceinline__ void store_mask(int N, uint8_t* orow, int c0) const {
     using M = typename Chunk<VW>::M;
@@ -789,27 +809,25 @@ __global__ __launch_bounds__(256) void decode_greedy_kernel(
   // hoisted into registers across row groups -- r04: certified 71 -> fewer VGPRs)
   const int64_t base = wid * RPW;
   if (base >= B) return;  // wave-uniform
-  do {
-    const int64_t row = base + grp;
-    const bool valid = row < B;
-    const int64_t r = valid ? row : 0;
-    GreedyRow<RL, EPL, VW> g;
-    const float* lrow = logits + r * lstride;
-    const uint8_t* mrow = mask ? mask + r * (int64_t)N : nullptr;
-    g.load(valid, N, lrow, mrow, c0);
-    float lp, L;
-    const int sel = greedy_row<OPT>(g, valid, N, clip, temp, sl, c0, group_scratch<RL, EPL>(lds, grp),
-                                    L, lp, lrow, mrow);
-    if (!valid) continue;
-    if (full) g.store_logp(N, L, full + r * (int64_t)N, c0);
-    if (sl == 0) {
-      // L is finite or NaN (the exp-sum is >= 1 unless NaN); finite means the argmax
-      // element is unmasked, NaN means index 0 was taken
-      if (mask && L != L && !g.allowed(0)) set_status(status, CO_ST_INFEASIBLE);
-      action_out[r] = sel;
-      if (logp_sel) logp_sel[r] = lp;
-    }
-  } while (0);
+  const int64_t row = base + grp;
+  const bool valid = row < B;
+  const int64_t r = valid ? row : 0;
+  GreedyRow<RL, EPL, VW> g;
+  const float* lrow = logits + r * lstride;
+  const uint8_t* mrow = mask ? mask + r * (int64_t)N : nullptr;
+  g.load(valid, N, lrow, mrow, c0);
+  float lp, L;
+  const int sel = greedy_row<OPT>(g, valid, N, clip, temp, sl, c0, group_scratch<RL, EPL>(lds, grp),
+                                  L, lp, lrow, mrow);
+  if (!valid) return;
+  if (full) g.store_logp(N, L, full + r * (int64_t)N, c0);
+  if (sl == 0) {
+    // L is finite or NaN (the exp-sum is >= 1 unless NaN); finite means the argmax
+    // element is unmasked, NaN means index 0 was taken
+    if (mask && L != L && !g.allowed(0)) set_status(status, CO_ST_INFEASIBLE);
+    action_out[r] = sel;
+    if (logp_sel) logp_sel[r] = lp;
+  }
 }
 
 template <int RL, int EPL, bool VEC, int OPT>
@@ -828,174 +846,26 @@ __global__ __launch_bounds__(256) void decode_kernel(int64_t B, int N, const flo
   // hoisted into registers across row groups -- r04: certified 71 -> fewer VGPRs)
   const int64_t base = wid * RPW;
   if (base >= B) return;  // wave-uniform
-  do {
-    const int64_t row = base + grp;
-    const bool valid = row < B;
-    const int64_t r = valid ? row : 0;
-    const int64_t a_in = (mode == CO_DECODE_EVALUATE && valid) ? action_in[r] : 0;
-    DecodeRow<RL, EPL, VEC, OPT> d;
-    d.run(valid, N, logits + r * lstride, mask ? mask + r * (int64_t)N : nullptr, clip, temp,
-          mode, a_in, seed, offset, row, sl, grp, group_scratch<RL, EPL>(lds, grp), top_k, top_p);
-    if (!valid) continue;
-    if (full) {
+  const int64_t row = base + grp;
+  const bool valid = row < B;
+  const int64_t r = valid ? row : 0;
+  const int64_t a_in = (mode == CO_DECODE_EVALUATE && valid) ? action_in[r] : 0;
+  DecodeRow<RL, EPL, VEC, OPT> d;
+  d.run(valid, N, logits + r * lstride, mask ? mask + r * (int64_t)N : nullptr, clip, temp,
+        mode, a_in, seed, offset, row, sl, grp, group_scratch<RL, EPL>(lds, grp), top_k, top_p);
+  if (!valid) return;
+  if (full) {
 #pragma unroll
-      for (int k = 0; k < EPL; ++k)
-        if (sl * EPL + k < N) full[r * (int64_t)N + sl * EPL + k] = d.x[k];
-    }
-    if (sl == 0) {
-      if (mode == CO_DECODE_EVALUATE && (a_in < 0 || a_in >= N))
-        set_status(status, CO_ST_INDEX_RANGE);
-      if (mode != CO_DECODE_EVALUATE && mask && !d.feas) set_status(status, CO_ST_INFEASIBLE);
-      action_out[r] = mode == CO_DECODE_EVALUATE ? a_in : (int64_t)d.sel;
-      if (logp_sel) logp_sel[r] = d.lp;
-    }
-  } while (0);
-}
-
-// Decode step fused with TSPEnv._step: the row's logits and action_mask are read once;
-// the selected action's env transition (tsp/env.py:67-93) is applied by the same lane
-// group: mask_out = mask_in minus the action, done = nothing left (group ballot),
-// i + 1, first_node.  654 B per TSP-100 row-step.
-template <int RL, int EPL, bool VEC, int OPT, int UNR = CO_DECODE_UNR>
-__global__ __launch_bounds__(256) void tsp_decode_step_kernel(
-    int64_t B, int N, const float* __restrict__ logits, int64_t lstride,
-    const uint8_t* __restrict__ mask_in, float clip, float temp, int mode,
-    const int64_t* __restrict__ action_in, int64_t* __restrict__ action_out,
-    float* __restrict__ logp_sel, uint64_t seed, uint64_t offset, uint8_t* __restrict__ mask_out,
-    const int64_t* __restrict__ i_in, int64_t* __restrict__ i_out,
-    const int64_t* __restrict__ first_in, int64_t* __restrict__ first_out, int take_first,
-    uint8_t* __restrict__ done, uint8_t* __restrict__ step_reward, float* __restrict__ ll_accum,
-    int32_t* status) {
-  constexpr int RPW = 64 / RL;
-  __shared__ __attribute__((aligned(16))) float lds[4 * 64 * EPL];
-  const int lane = lane_id(), sl = lane % RL, grp = lane / RL;
-  const int64_t wid = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
-  const unsigned long long gmask = RL == 64 ? ~0ull : (((1ull << RL) - 1ull) << (grp * RL));
-  // UNR rows per lane group per iteration: every load of all UNR rows (logits, mask,
-  // i, first_node, action, ll accumulator) is issued before any row's math
-  // one row group per wave: the grid covers B (no grid-stride loop, so no values are
-  // hoisted into registers across row groups -- r04: certified 71 -> fewer VGPRs)
-  const int64_t base = wid * RPW * UNR;
-  if (base >= B) return;  // wave-uniform
-  do {
-    DecodeRow<RL, EPL, VEC, OPT> d[UNR];
-    int64_t rr[UNR], ain[UNR], iv[UNR], fv[UNR];
-    bool vv[UNR];
-    float acc[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int64_t row = base + u * RPW + grp;
-      vv[u] = row < B;
-      rr[u] = vv[u] ? row : 0;
-      ain[u] = (mode == CO_DECODE_EVALUATE && vv[u]) ? action_in[rr[u]] : 0;
-      iv[u] = vv[u] ? i_in[rr[u]] : 0;
-      fv[u] = (vv[u] && !take_first) ? first_in[rr[u]] : 0;
-      acc[u] = (vv[u] && ll_accum) ? ll_accum[rr[u]] : 0.f;
-      d[u].load(vv[u], N, logits + rr[u] * lstride, mask_in + rr[u] * (int64_t)N, sl);
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const bool valid = vv[u];
-      const int64_t r = rr[u], a_in = ain[u];
-      d[u].compute(valid, N, clip, temp, mode, a_in, seed, offset, base + u * RPW + grp, sl,
-                   grp, group_scratch<RL, EPL>(lds, grp));
-      bool any_left = false;
-      uint8_t* orow = mask_out + r * (int64_t)N;
-      const int c0 = sl * EPL;
-#pragma unroll
-      for (int k = 0; k < EPL; ++k) {
-        if (c0 + k == d[u].sel) d[u].mk[k] = 0;
-        any_left |= (valid && c0 + k < N && d[u].mk[k] != 0);
-      }
-      if (VEC) {
-#pragma unroll
-        for (int j = 0; j < EPL / 4; ++j)
-          if (valid && c0 + 4 * j < N)
-            *reinterpret_cast<uint32_t*>(orow + c0 + 4 * j) =
-                (uint32_t)d[u].mk[4 * j] | ((uint32_t)d[u].mk[4 * j + 1] << 8) |
-                ((uint32_t)d[u].mk[4 * j + 2] << 16) | ((uint32_t)d[u].mk[4 * j + 3] << 24);
-      } else {
-#pragma unroll
-        for (int k = 0; k < EPL; ++k)
-          if (valid && c0 + k < N) orow[c0 + k] = d[u].mk[k];
-      }
-      const bool left = (__ballot(any_left) & gmask) != 0;
-      if (valid && sl == 0) {
-        if (mode == CO_DECODE_EVALUATE && (a_in < 0 || a_in >= N))
-          set_status(status, CO_ST_INDEX_RANGE);
-        if (mode != CO_DECODE_EVALUATE && !d[u].feas) set_status(status, CO_ST_INFEASIBLE);
-        const int64_t a = mode == CO_DECODE_EVALUATE ? a_in : (int64_t)d[u].sel;
-        action_out[r] = a;
-        if (logp_sel) logp_sel[r] = d[u].lp;
-        if (ll_accum) ll_accum[r] = acc[u] + d[u].lp;  // get_log_likelihood's sum, per step
-        i_out[r] = iv[u] + 1;
-        first_out[r] = take_first ? a : fv[u];
-        done[r] = !left;
-        step_reward[r] = 0;
-      }
-    }
-  } while (0);
-}
-
-// Greedy decode step fused with TSPEnv._step on the GreedyRow engine (the POMO /
-// multistart-greedy hot loop); same outputs as tsp_decode_step_kernel in greedy mode.
-// The mask words are updated in registers (the selected byte cleared) and stored back.
-template <int RL, int EPL, int VW, int OPT>
-__global__ __launch_bounds__(256) void tsp_decode_greedy_kernel(
-    int64_t B, int N, const float* __restrict__ logits, int64_t lstride,
-    const uint8_t* __restrict__ mask_in, float clip, float temp, int64_t* __restrict__ action_out,
-    float* __restrict__ logp_sel, uint8_t* __restrict__ mask_out, const int64_t* __restrict__ i_in,
-    int64_t* __restrict__ i_out, const int64_t* __restrict__ first_in,
-    int64_t* __restrict__ first_out, int take_first, uint8_t* __restrict__ done,
-    uint8_t* __restrict__ step_reward, float* __restrict__ ll_accum, int32_t* status) {
-  constexpr int RPW = 64 / RL;
-  __shared__ __attribute__((aligned(16))) float lds[4 * 64 * EPL];
-  const int lane = lane_id(), sl = lane % RL, grp = lane / RL, c0 = sl * EPL;
-  const int64_t wid = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
-  const unsigned long long gmask = RL == 64 ? ~0ull : (((1ull << RL) - 1ull) << (grp * RL));
-  // one row group per wave: the grid covers B (no grid-stride loop, so no values are
-  // hoisted into registers across row groups -- r04: certified 71 -> fewer VGPRs)
-  const int64_t base = wid * RPW;
-  if (base >= B) return;  // wave-uniform
-  do {
-    const int64_t row = base + grp;
-    const bool valid = row < B;
-    const int64_t r = valid ? row : 0;
-    int64_t iv = 0, fv = 0;
-    float acc = 0.f;
-    if (valid && sl == 0) {
-      iv = i_in[r];
-      if (!take_first) fv = first_in[r];
-      if (ll_accum) acc = ll_accum[r];
-    }
-    GreedyRow<RL, EPL, VW> g;
-    const float* lrow = logits + r * lstride;
-    const uint8_t* mrow = mask_in + r * (int64_t)N;
-    g.load(valid, N, lrow, mrow, c0);
-    float lp, L;
-    const int sel = greedy_row<OPT>(g, valid, N, clip, temp, sl, c0,
-                                           group_scratch<RL, EPL>(lds, grp), L, lp, lrow, mrow);
-    const bool feas0 = g.allowed(0);
-    uint32_t left = 0u;
-#pragma unroll
-    for (int j = 0; j < EPL / 4; ++j) {
-      const int off = sel - (c0 + 4 * j);
-      if ((unsigned)off < 4u) g.mw[j] &= ~(0xffu << (8 * off));
-      left |= g.mw[j];
-    }
-    if (valid) g.store_mask(N, mask_out + r * (int64_t)N, c0);
-    const bool any_left = (__ballot(left != 0u) & gmask) != 0;
-    if (valid && sl == 0) {
-      if (L != L && !feas0) set_status(status, CO_ST_INFEASIBLE);
-      action_out[r] = sel;
-      if (logp_sel) logp_sel[r] = lp;
-      if (ll_accum) ll_accum[r] = acc + lp;  // get_log_likelihood's sum, per step
-      i_out[r] = iv + 1;
-      first_out[r] = take_first ? (int64_t)sel : fv;
-      done[r] = !any_left;
-      step_reward[r] = 0;
-    }
-  } while (0);
+    for (int k = 0; k < EPL; ++k)
+      if (sl * EPL + k < N) full[r * (int64_t)N + sl * EPL + k] = d.x[k];
+  }
+  if (sl == 0) {
+    if (mode == CO_DECODE_EVALUATE && (a_in < 0 || a_in >= N))
+      set_status(status, CO_ST_INDEX_RANGE);
+    if (mode != CO_DECODE_EVALUATE && mask && !d.feas) set_status(status, CO_ST_INFEASIBLE);
+    action_out[r] = mode == CO_DECODE_EVALUATE ? a_in : (int64_t)d.sel;
+    if (logp_sel) logp_sel[r] = d.lp;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1204,16 +1074,34 @@ __global__ __launch_bounds__(kLongThreads) void decode_long_kernel(
 
 }  // namespace
 
-// RL lanes x EPL consecutive elements per row, by row-length bucket (CO_RL* above).
-#define CO_ROW_DISPATCH(LAUNCH, V)                           \
-  if (N <= 16) LAUNCH(CO_RL16, 16 / CO_RL16, V);             \
-  else if (N <= 32) LAUNCH(CO_RL32, 32 / CO_RL32, V);        \
-  else if (N <= 64) LAUNCH(CO_RL64, 64 / CO_RL64, V);        \
-  else if (N <= 128) LAUNCH(CO_RL128, 128 / CO_RL128, V);    \
-  else if (N <= 256) LAUNCH(CO_RL256, 256 / CO_RL256, V);    \
-  else if (N <= 512) LAUNCH(64, 8, V);                       \
-  else if (N <= 1024) LAUNCH(64, 16, V);                     \
-  else LAUNCH(64, 32, V)
+// The row-bucket table: a row of N <= kRowCap[i] columns runs on kRowLanes[i] lanes of
+// kRowCap[i] / kRowLanes[i] consecutive elements each (CO_RL* above).  The dispatch, the
+// grid and the fused env steps' LDS sizing all read it.
+constexpr int kRowBuckets = 8;
+constexpr int kRowCap[kRowBuckets] = {16, 32, 64, 128, 256, 512, 1024, 2048};
+constexpr int kRowLanes[kRowBuckets] = {CO_RL16, CO_RL32, CO_RL64, CO_RL128, CO_RL256, 64, 64, 64};
+struct RowBucket {
+  int rl, epl;
+  constexpr int rows_per_wave() const { return 64 / rl; }
+  constexpr int greedy_epl() const { return epl < 4 ? 4 : epl; }  // GreedyRow's u32 mask words
+};
+constexpr RowBucket row_bucket_at(int i) { return {kRowLanes[i], kRowCap[i] / kRowLanes[i]}; }
+constexpr RowBucket row_bucket(int64_t N) {
+  int i = 0;
+  while (i < kRowBuckets - 1 && N > kRowCap[i]) ++i;
+  return row_bucket_at(i);
+}
+
+#define CO_ROW_CASE(LAUNCH, V, I) LAUNCH(row_bucket_at(I).rl, row_bucket_at(I).epl, V)
+#define CO_ROW_DISPATCH(LAUNCH, V)                       \
+  if (N <= kRowCap[0]) CO_ROW_CASE(LAUNCH, V, 0);        \
+  else if (N <= kRowCap[1]) CO_ROW_CASE(LAUNCH, V, 1);   \
+  else if (N <= kRowCap[2]) CO_ROW_CASE(LAUNCH, V, 2);   \
+  else if (N <= kRowCap[3]) CO_ROW_CASE(LAUNCH, V, 3);   \
+  else if (N <= kRowCap[4]) CO_ROW_CASE(LAUNCH, V, 4);   \
+  else if (N <= kRowCap[5]) CO_ROW_CASE(LAUNCH, V, 5);   \
+  else if (N <= kRowCap[6]) CO_ROW_CASE(LAUNCH, V, 6);   \
+  else CO_ROW_CASE(LAUNCH, V, 7)
 
 // the uniform clip / temperature / fast-math options as the OPT template flags
 #define CO_OPT_CASE(V, LAUNCH, KERNEL, ...) \
@@ -1254,11 +1142,22 @@ __global__ __launch_bounds__(kLongThreads) void decode_long_kernel(
   } while (0)
 
 inline unsigned decode_grid(int64_t B, int N, int unr = 1) {
-  const int rl = N <= 16 ? CO_RL16 : N <= 32 ? CO_RL32 : N <= 64 ? CO_RL64
-               : N <= 128 ? CO_RL128 : N <= 256 ? CO_RL256 : 64;
-  const int64_t waves = ((B + unr - 1) / unr * rl + 63) / 64;
+  const int64_t waves = ((B + unr - 1) / unr * row_bucket(N).rl + 63) / 64;
   return cover_grid(waves, 4);  // every row group gets its wave; 0: B too large
 }
+
+// The mode word of the decode entry points: CO_DECODE_GREEDY / SAMPLING / EVALUATE plus the
+// CO_DECODE_FAST and CO_DECODE_CERTIFIED flags (FAST wins over CERTIFIED).
+struct DecodeMode {
+  int mode;  // the flags stripped
+  bool cert, fast;
+  bool parse(int word) {  // false: CO_E_MODE
+    cert = (word & CO_DECODE_CERTIFIED) != 0 && (word & CO_DECODE_FAST) == 0;
+    fast = (word & CO_DECODE_FAST) != 0;
+    mode = word & ~(CO_DECODE_FAST | CO_DECODE_CERTIFIED);
+    return mode >= 0 && mode <= 2;
+  }
+};
 
 // widest GreedyRow load (4 / 2 / 1 elements) the row length, stride and pointers allow
 inline int greedy_vw(int64_t N, int64_t lstride, const float* logits, const uint8_t* m_in,

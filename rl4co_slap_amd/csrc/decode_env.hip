@@ -8,16 +8,16 @@
 //   * CVRP (cvrp/env.py:73-149): used = (used + demand[clamp(a-1)]) * (a != 0), visited[a]
 //     = 1, done = sum(visited) == N+1, reward = 0, and get_action_mask recomputed from the
 //     new state (the strict `demand + used > capacity` test, the depot rule).
-// The row engines are decode_common.hpp's (GreedyRow for greedy, certified by default;
-// DecodeRow for sampling / evaluate), with the same lane ownership: lane sl of an RL-lane
-// group owns the row's EPL consecutive columns c0 = sl*EPL .. c0+EPL-1.  The env's own
+// CVRP's kernels are decode_fused.hpp's bodies, SLAP's are hand-written; both run on
+// decode_common.hpp's row engines (GreedyRow for greedy, certified by default; DecodeRow for
+// sampling / evaluate), with the same lane ownership: lane sl of an RL-lane group owns the row's EPL consecutive columns c0 = sl*EPL .. c0+EPL-1.  The env's own
 // per-column data (SLAP: nothing; CVRP: the visited bytes and demand[c-1] of those
 // columns) is loaded by the same lanes in the same 4-column chunks, issued together with
 // the logits, so the transition needs no second memory round trip: the selected
 // column's demand comes from its owner lane by one shuffle, the row sums (visited count,
 // "any customer feasible") are group reductions.  Outputs are the two-launch path's
 // (co_decode_step + co_slap_step / co_cvrp_step) bit for bit, RNG use included.
-#include "decode_common.hpp"
+#include "decode_fused.hpp"
 
 namespace {
 
@@ -130,6 +130,11 @@ struct SlapStage {
   }
 };
 
+// SLAP keeps its two hand-written kernels, instruction for instruction (their machine code is
+// the parent's, byte for byte): on decode_fused.hpp's bodies the certified greedy launch at
+// B = 65,536 measured 12.16-12.35 us against the old kernel's 12.03-12.19 in three calls out
+// of four, over the refactor's speed gate, with near-identical IR (the stage base in dwords
+// and the order of the lane arithmetic).  The greedy kernel's stage base stays in bytes.
 // Greedy (GreedyRow; certified / exact / fast per OPT) decode + SLAP step.
 template <int RL, int EPL, int VW, int OPT>
 __global__ __launch_bounds__(256) void slap_decode_greedy_kernel(
@@ -270,17 +275,25 @@ __host__ __device__ inline int cvrp_stage_dwords(int rpw, int N) {  // 16-byte m
   return (rpw * N + cvrp_vis_dwords(rpw, N) + 3 * rpw + 3) & ~3;
 }
 
+// The env-step type of CVRP (decode_fused.hpp): the arguments and the wave's stage.
 template <int RL, int EPL>
-struct CvrpStage {
+struct CvrpStep {
+  static constexpr int kDiagCut = kDiagCvrpCut;
   static constexpr int RPW = 64 / RL;
-  uint32_t* s;
-  int N;
+  CvrpEpi e;
+  uint32_t* s;  // the wave's stage
+  __device__ __forceinline__ static CvrpStep of(const CvrpEpi& e, uint32_t* stage) {
+    return {e, stage + wave_in_block() * cvrp_stage_dwords(RPW, e.N)};
+  }
   __device__ __forceinline__ uint32_t* dem() const { return s; }
-  __device__ __forceinline__ uint32_t* vis() const { return s + RPW * N; }
-  __device__ __forceinline__ uint32_t* sc() const { return s + RPW * N + cvrp_vis_dwords(RPW, N); }
+  __device__ __forceinline__ uint32_t* vis() const { return s + RPW * e.N; }
+  __device__ __forceinline__ uint32_t* sc() const {
+    return s + RPW * e.N + cvrp_vis_dwords(RPW, e.N);
+  }
 
-  __device__ __forceinline__ void issue(const CvrpEpi& e, int64_t base, int nr) const {
-    const int Nn = N, NC = N + 1;
+  __device__ __forceinline__ void fetch(int64_t base, int64_t B, int, bool) const {
+    const int nr = (int)(B - base < RPW ? B - base : RPW);
+    const int Nn = e.N, NC = e.N + 1;
     const float* dsrc = e.demand + base * Nn;
     const int nd = nr * Nn;
     if ((reinterpret_cast<uintptr_t>(dsrc) & 15) == 0) {  // wave-uniform
@@ -306,9 +319,12 @@ struct CvrpStage {
   // cvrp/env.py:73-105 + get_action_mask (:137-149) for action a_raw of row r (group g),
   // the same arithmetic as co_cvrp_step, on the staged row.  Group-wide (every lane of the
   // wave active); writes the visited / mask rows and (sl == 0) the row scalars.
-  __device__ __forceinline__ void apply(const CvrpEpi& e, bool valid, int64_t r, int g, int sl,
-                                        int c0, int64_t a_raw, int32_t* status) const {
-    const int Nn = N, NC = N + 1;
+  template <class Row>
+  __device__ __forceinline__ bool apply(Row&, bool valid, int64_t r, int g, int sl, int c0,
+                                        int64_t a_raw, int, int32_t* status) const {
+    stage_ready();
+    if (kDiagCut == 1) return true;  // timing cut: no transition
+    const int Nn = e.N, NC = e.N + 1;
     const float* dm_s = reinterpret_cast<const float*>(dem()) + g * Nn;
     const float used = __uint_as_float(sc()[g]), cap = __uint_as_float(sc()[RPW + g]);
     const bool bad = a_raw < 0 || a_raw > Nn;
@@ -361,7 +377,7 @@ struct CvrpStage {
     cnt = grp_reduce<RL>(cnt, [](uint32_t x, uint32_t y) { return x + y; });
     const uint64_t gm = RL == 64 ? ~0ull : ((1ull << RL) - 1ull);
     const bool anyf = ((__ballot(feas) >> (RL * g)) & gm) != 0ull;
-    if (!valid) return;
+    if (!valid) return true;
     if (sl == 0) mk[0] |= (uint32_t) !((a_raw == 0) && anyf);  // cvrp/env.py:146-148
     using M = typename Chunk<3>::M;
     uint8_t* vdst = e.vis_out + r * (int64_t)NC;
@@ -388,8 +404,11 @@ struct CvrpStage {
       e.done[r] = (int)cnt == NC;
       e.reward[r] = 0;
     }
+    return true;  // (an action out of range is reported above)
   }
-  __device__ __forceinline__ float ll_of(int g) const { return __uint_as_float(sc()[2 * RPW + g]); }
+  __device__ __forceinline__ float* ll_out() const { return e.ll_accum; }
+  __device__ __forceinline__ float ll_in(int g) const { return __uint_as_float(sc()[2 * RPW + g]); }
+  __device__ __forceinline__ void store_row(int64_t, int, int64_t) const {}  // all in apply
 };
 
 template <int RL, int EPL, int VW, int OPT>
@@ -397,43 +416,10 @@ __global__ __launch_bounds__(256) void cvrp_decode_greedy_kernel(
     int64_t B, int NC, const float* __restrict__ logits, int64_t lstride,
     const uint8_t* __restrict__ mask_in, float clip, float temp, int64_t* __restrict__ action_out,
     float* __restrict__ logp_sel, int32_t* status, CvrpEpi e) {
-  constexpr int RPW = 64 / RL;
   __shared__ __attribute__((aligned(16))) float lds[4 * 64 * EPL];
   extern __shared__ __attribute__((aligned(16))) uint32_t s_stage[];
-  const int lane = lane_id(), sl = lane % RL, grp = lane / RL, c0 = sl * EPL;
-  const CvrpStage<RL, EPL> st{s_stage + wave_in_block() * cvrp_stage_dwords(RPW, e.N), e.N};
-  // one row group per wave (the grid covers B: no loop, so nothing is hoisted into
-  // registers across row groups)
-  const int64_t wid = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
-  const int64_t base = wid * RPW;
-  if (base >= B) return;  // wave-uniform
-  {
-    const int nr = (int)(B - base < RPW ? B - base : RPW);
-    st.issue(e, base, nr);
-    const int64_t row = base + grp;
-    const bool valid = row < B;
-    const int64_t r = valid ? row : 0;
-    GreedyRow<RL, EPL, VW> g;
-    const float* lrow = logits + r * lstride;
-    const uint8_t* mrow = mask_in + r * (int64_t)NC;
-    g.load(valid, NC, lrow, mrow, c0);
-    float lp = 0.f, lse = 0.f;
-    int sel = (int)(row % NC);
-    if (kDiagCvrpCut != 2)
-      sel = greedy_row<OPT>(g, valid, NC, clip, temp, sl, c0, group_scratch<RL, EPL>(lds, grp),
-                            lse, lp, lrow, mrow);
-    else
-      lp = g.v[0];  // keep the loads
-    const bool feas0 = g.allowed(0);
-    stage_ready();
-    if (kDiagCvrpCut != 1) st.apply(e, valid, r, grp, sl, c0, sel, status);
-    if (valid && sl == 0) {
-      if (lse != lse && !feas0) set_status(status, CO_ST_INFEASIBLE);
-      action_out[r] = sel;
-      if (logp_sel) logp_sel[r] = lp;
-      if (e.ll_accum) e.ll_accum[r] = st.ll_of(grp) + lp;
-    }
-  }
+  fused_greedy_body<RL, EPL, VW, OPT>(lds, B, NC, logits, lstride, mask_in, clip, temp, action_out,
+                                      logp_sel, status, CvrpStep<RL, EPL>::of(e, s_stage));
 }
 
 template <int RL, int EPL, bool VEC, int OPT>
@@ -442,55 +428,14 @@ __global__ __launch_bounds__(256) void cvrp_decode_step_kernel(
     const uint8_t* __restrict__ mask_in, float clip, float temp, int mode,
     const int64_t* __restrict__ action_in, int64_t* __restrict__ action_out,
     float* __restrict__ logp_sel, uint64_t seed, uint64_t offset, int32_t* status, CvrpEpi e) {
-  constexpr int RPW = 64 / RL;
   __shared__ __attribute__((aligned(16))) float lds[4 * 64 * EPL];
   extern __shared__ __attribute__((aligned(16))) uint32_t s_stage[];
-  const int lane = lane_id(), sl = lane % RL, grp = lane / RL, c0 = sl * EPL;
-  const CvrpStage<RL, EPL> st{s_stage + wave_in_block() * cvrp_stage_dwords(RPW, e.N), e.N};
-  // one row group per wave (the grid covers B: no loop, so nothing is hoisted into
-  // registers across row groups)
-  const int64_t wid = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
-  const int64_t base = wid * RPW;
-  if (base >= B) return;  // wave-uniform
-  {
-    const int nr = (int)(B - base < RPW ? B - base : RPW);
-    st.issue(e, base, nr);
-    const int64_t row = base + grp;
-    const bool valid = row < B;
-    const int64_t r = valid ? row : 0;
-    const int64_t a_in = (mode == CO_DECODE_EVALUATE && valid) ? action_in[r] : 0;
-    DecodeRow<RL, EPL, VEC, OPT> d;
-    d.run(valid, NC, logits + r * lstride, mask_in + r * (int64_t)NC, clip, temp, mode, a_in,
-          seed, offset, row, sl, grp, group_scratch<RL, EPL>(lds, grp));
-    const int64_t a_raw = mode == CO_DECODE_EVALUATE ? a_in : (int64_t)d.sel;
-    stage_ready();
-    st.apply(e, valid, r, grp, sl, c0, a_raw, status);
-    if (valid && sl == 0) {
-      if (mode == CO_DECODE_EVALUATE && (a_in < 0 || a_in >= NC))
-        set_status(status, CO_ST_INDEX_RANGE);
-      if (mode != CO_DECODE_EVALUATE && !d.feas) set_status(status, CO_ST_INFEASIBLE);
-      action_out[r] = a_raw;
-      if (logp_sel) logp_sel[r] = d.lp;
-      if (e.ll_accum) e.ll_accum[r] = st.ll_of(grp) + d.lp;
-    }
-  }
+  fused_step_body<RL, EPL, VEC, OPT>(lds, B, NC, logits, lstride, mask_in, clip, temp, mode,
+                                        action_in, action_out, logp_sel, seed, offset, status,
+                                        CvrpStep<RL, EPL>::of(e, s_stage));
 }
 
 }  // namespace
-
-// lanes per row of the register row engines (decode_common.hpp's buckets)
-inline int row_lanes(int64_t N) {
-  return N <= 16 ? CO_RL16 : N <= 32 ? CO_RL32 : N <= 64 ? CO_RL64 : N <= 128 ? CO_RL128
-       : N <= 256 ? CO_RL256 : 64;
-}
-inline int row_epl(int64_t N) {
-  const int rl = row_lanes(N);
-  const int b = N <= 16 ? 16 : N <= 32 ? 32 : N <= 64 ? 64 : N <= 128 ? 128 : N <= 256 ? 256
-              : N <= 512 ? 512 : N <= 1024 ? 1024 : 2048;
-  const int e = b / rl;
-  return e < 4 ? 4 : e;
-}
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 extern "C" int co_slap_decode_step(int64_t B, int64_t L, int64_t P, const float* logits,
                                    int64_t lstride, const uint8_t* mask_in, float clip, float temp,
@@ -502,65 +447,40 @@ extern "C" int co_slap_decode_step(int64_t B, int64_t L, int64_t P, const float*
                                    uint8_t* done, uint8_t* step_reward, float* ll_accum,
                                    int32_t* status, void* stream) {
   if (B < 0 || L <= 0 || L > 64 * 32 || P <= 0 || P > (1 << 24)) return CO_E_INVAL;
-  const int mword = mode;
-  const bool cert = (mode & CO_DECODE_CERTIFIED) != 0 && (mode & CO_DECODE_FAST) == 0;
-  const bool fast = (mode & CO_DECODE_FAST) != 0;
-  mode &= ~(CO_DECODE_FAST | CO_DECODE_CERTIFIED);
-  if (mode < 0 || mode > 2) return CO_E_MODE;
+  FusedDecode f{B,         L,          logits,   lstride, mask_in, clip,     temp,   mode,
+                action_in, action_out, logp_sel, seed,    offset,  mask_out, status, stream};
+  if (!f.parse()) return CO_E_MODE;
   if (B == 0) return CO_OK;
-  if (!logits || !mask_in || !action_out || !assign_in || !assign_out || !mask_out || !i_in ||
-      !i_out || !done || !step_reward || (mode == CO_DECODE_EVALUATE && !action_in) ||
+  if (!f.pointers_ok() || !assign_in || !assign_out || !i_in || !i_out || !done || !step_reward ||
       (!to_choose && (tc_stride < 0 || tc_stride >= P)))
     return CO_E_INVAL;
   // mask_out may be mask_in: a row's mask is read (and re-read by the certified fallback)
   // by its own lane group before the transition stores it, after the wave's stage barrier
-  const int64_t N = L;  // the row-dispatch macros' name for the row length
-  const int rpw = 64 / row_lanes(N);
-  const size_t shmem = (size_t)4 * slap_stage_dwords(rpw, (int)P) * 4;
-  const size_t lds_static = (size_t)4 * 64 * row_epl(N) * 4;
-  if (shmem + lds_static > 64 * 1024 || (to_choose && !aligned4(to_choose)) || !aligned4(assign_in) ||
-      !aligned4(i_in) || (ll_accum && !aligned4(ll_accum))) {
-    // beyond the stage (huge P) or misaligned: the two launches it fuses
-    if (ll_accum) return CO_E_INVAL;
-    int rc = co_decode_step(B, L, logits, lstride, mask_in, clip, temp, mword, action_in,
-                            action_out, logp_sel, nullptr, seed, offset, status, stream);
-    if (rc != CO_OK) return rc;
-    return co_slap_step(B, L, P, mode == CO_DECODE_EVALUATE ? action_in : action_out, to_choose,
-                        tc_stride, assign_in, assign_out, mask_in, mask_out, i_in, i_out, done,
-                        step_reward, status, stream);
-  }
+  const int stage = slap_stage_dwords(f.rows_per_wave(), (int)P);
+  if (!f.stage_fits(stage) || (to_choose && !aligned4(to_choose)) || !aligned4(assign_in) ||
+      !aligned4(i_in) || (ll_accum && !aligned4(ll_accum)))  // huge P or misaligned
+    return f.two_launches(ll_accum, [&](const int64_t* actions) {
+      return co_slap_step(B, L, P, actions, to_choose, tc_stride, assign_in, assign_out, mask_in,
+                          mask_out, i_in, i_out, done, step_reward, status, stream);
+    });
   const SlapEpi epi{(int)P, to_choose, tc_stride, assign_in, assign_out, mask_out,
                     i_in,   i_out,     done,      step_reward, ll_accum};
+  const size_t shmem = FusedDecode::stage_bytes(stage);
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(cover_grid(B, rpw * 4)), block(256);
-  if (grid.x == 0) return CO_E_INVAL;
-  if (mode == CO_DECODE_GREEDY) {
-#define CO_SDG(RL, EPL, V)                                                                     \
-  CO_OPT_DISPATCH_G(hipLaunchKernelGGL,                                                        \
-                    (slap_decode_greedy_kernel<RL, (EPL < 4 ? 4 : EPL), V, OPT>), grid, block, \
-                    shmem, s, B, (int)N, logits, lstride, mask_in, clip, temp, action_out,     \
-                    logp_sel, status, epi)
-    switch (greedy_vw(N, lstride, logits, mask_in, mask_out, nullptr)) {
-      case 4: CO_ROW_DISPATCH(CO_SDG, 4); break;
-      case 2: CO_SDG(CO_RL16, 16 / CO_RL16, 2); break;  // N < 4
-      default: CO_ROW_DISPATCH(CO_SDG, 3);
-    }
-#undef CO_SDG
-    return launch_status();
-  }
-#define CO_SDS(RL, EPL, V)                                                                     \
-  CO_OPT_DISPATCH(hipLaunchKernelGGL, (slap_decode_step_kernel<RL, EPL, V, OPT>), grid, block, \
-                  shmem, s, B, (int)N, logits, lstride, mask_in, clip, temp, mode, action_in,   \
-                  action_out, logp_sel, seed, offset, status, epi)
-  if (decode_vec_ok(logits, lstride, mask_in, N) &&
-      (reinterpret_cast<uintptr_t>(mask_out) & 3) == 0) {
-    CO_ROW_DISPATCH(CO_SDS, true);
-  } else {
-    CO_ROW_DISPATCH(CO_SDS, false);
-  }
-#undef CO_SDS
-  (void)cert;
-  return launch_status();
+  return f.launch(
+      1, aligned4(mask_out),
+      [&](auto c, dim3 grid) {
+        using C = decltype(c);
+        hipLaunchKernelGGL((slap_decode_greedy_kernel<C::RL, C::EPL, C::V, C::OPT>), grid,
+                           dim3(256), shmem, s, B, (int)L, logits, lstride, mask_in, clip, temp,
+                           action_out, logp_sel, status, epi);
+      },
+      [&](auto c, dim3 grid) {
+        using C = decltype(c);
+        hipLaunchKernelGGL((slap_decode_step_kernel<C::RL, C::EPL, C::V, C::OPT>), grid, dim3(256),
+                           shmem, s, B, (int)L, logits, lstride, mask_in, clip, temp, f.m.mode,
+                           action_in, action_out, logp_sel, seed, offset, status, epi);
+      });
 }
 
 extern "C" int co_cvrp_decode_step(int64_t B, int64_t Ncust, const float* logits,
@@ -573,65 +493,43 @@ extern "C" int co_cvrp_decode_step(int64_t B, int64_t Ncust, const float* logits
                                    uint8_t* mask_out, float* ll_accum, int32_t* status,
                                    void* stream) {
   if (B < 0 || Ncust <= 0 || Ncust + 1 > 64 * 32) return CO_E_INVAL;
-  const int mword = mode;
-  const bool cert = (mode & CO_DECODE_CERTIFIED) != 0 && (mode & CO_DECODE_FAST) == 0;
-  const bool fast = (mode & CO_DECODE_FAST) != 0;
-  mode &= ~(CO_DECODE_FAST | CO_DECODE_CERTIFIED);
-  if (mode < 0 || mode > 2) return CO_E_MODE;
+  const int64_t N = Ncust + 1;  // row length (depot + customers)
+  FusedDecode f{B,         N,          logits,   lstride, mask_in, clip,     temp,   mode,
+                action_in, action_out, logp_sel, seed,    offset,  mask_out, status, stream};
+  if (!f.parse()) return CO_E_MODE;
   if (B == 0) return CO_OK;
-  if (!logits || !mask_in || !action_out || !demand || !used_in || !used_out || !vcap ||
-      !vis_in || !vis_out || !done || !step_reward || !mask_out ||
-      (mode == CO_DECODE_EVALUATE && !action_in))
+  if (!f.pointers_ok() || !demand || !used_in || !used_out || !vcap || !vis_in || !vis_out ||
+      !done || !step_reward)
     return CO_E_INVAL;
   // every lane reads its own columns of the input rows before any lane writes: in-place
   // visited / mask rows are fine within a row, but a lane group's stores must not reach
   // another group's unread row, so the outputs are separate buffers
   if (mask_out == mask_in || vis_out == vis_in) return CO_E_INVAL;
-  const int64_t N = Ncust + 1;  // row length (depot + customers)
-  const int rpw = 64 / row_lanes(N);
-  const size_t shmem = (size_t)4 * cvrp_stage_dwords(rpw, (int)Ncust) * 4;
-  const size_t lds_static = (size_t)4 * 64 * row_epl(N) * 4;
-  if (shmem + lds_static > 64 * 1024 || (rpw * N) % 4 != 0 || !aligned4(vis_in) ||
+  const int stage = cvrp_stage_dwords(f.rows_per_wave(), (int)Ncust);
+  if (!f.stage_fits(stage) || (f.rows_per_wave() * N) % 4 != 0 || !aligned4(vis_in) ||
       !aligned4(demand) || !aligned4(used_in) || !aligned4(vcap) ||
-      (ll_accum && !aligned4(ll_accum))) {
-    // beyond the stage or misaligned rows: the two launches it fuses
-    if (ll_accum) return CO_E_INVAL;
-    int rc = co_decode_step(B, N, logits, lstride, mask_in, clip, temp, mword, action_in,
-                            action_out, logp_sel, nullptr, seed, offset, status, stream);
-    if (rc != CO_OK) return rc;
-    return co_cvrp_step(B, Ncust, mode == CO_DECODE_EVALUATE ? action_in : action_out, demand,
-                        used_in, used_out, vcap, vis_in, vis_out, cur_out, done, step_reward,
-                        mask_out, status, nullptr, stream);
-  }
+      (ll_accum && !aligned4(ll_accum)))  // beyond the stage or misaligned rows
+    return f.two_launches(ll_accum, [&](const int64_t* actions) {
+      return co_cvrp_step(B, Ncust, actions, demand, used_in, used_out, vcap, vis_in, vis_out,
+                          cur_out, done, step_reward, mask_out, status, nullptr, stream);
+    });
   const CvrpEpi epi{(int)Ncust, demand,  used_in, used_out,    vcap,     vis_in,
                     vis_out,    cur_out, done,    step_reward, mask_out, ll_accum};
+  const size_t shmem = FusedDecode::stage_bytes(stage);
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(cover_grid(B, rpw * 4)), block(256);
-  if (grid.x == 0) return CO_E_INVAL;
-  if (mode == CO_DECODE_GREEDY) {
-#define CO_CDG(RL, EPL, V)                                                                     \
-  CO_OPT_DISPATCH_G(hipLaunchKernelGGL,                                                        \
-                    (cvrp_decode_greedy_kernel<RL, (EPL < 4 ? 4 : EPL), V, OPT>), grid, block, \
-                    shmem, s, B, (int)N, logits, lstride, mask_in, clip, temp, action_out,     \
-                    logp_sel, status, epi)
-    switch (greedy_vw(N, lstride, logits, mask_in, mask_out, nullptr)) {
-      case 4: CO_ROW_DISPATCH(CO_CDG, 4); break;
-      case 2: CO_CDG(CO_RL16, 16 / CO_RL16, 2); break;  // N < 4
-      default: CO_ROW_DISPATCH(CO_CDG, 3);
-    }
-#undef CO_CDG
-    return launch_status();
-  }
-#define CO_CDS(RL, EPL, V)                                                                     \
-  CO_OPT_DISPATCH(hipLaunchKernelGGL, (cvrp_decode_step_kernel<RL, EPL, V, OPT>), grid, block, \
-                  shmem, s, B, (int)N, logits, lstride, mask_in, clip, temp, mode, action_in,   \
-                  action_out, logp_sel, seed, offset, status, epi)
-  if (decode_vec_ok(logits, lstride, mask_in, N)) {
-    CO_ROW_DISPATCH(CO_CDS, true);
-  } else {
-    CO_ROW_DISPATCH(CO_CDS, false);
-  }
-#undef CO_CDS
-  (void)cert;
-  return launch_status();
+  // (the transition stores the mask row itself: no condition of its own on the VEC path)
+  return f.launch(
+      1, true,
+      [&](auto c, dim3 grid) {
+        using C = decltype(c);
+        hipLaunchKernelGGL((cvrp_decode_greedy_kernel<C::RL, C::EPL, C::V, C::OPT>), grid,
+                           dim3(256), shmem, s, B, (int)N, logits, lstride, mask_in, clip, temp,
+                           action_out, logp_sel, status, epi);
+      },
+      [&](auto c, dim3 grid) {
+        using C = decltype(c);
+        hipLaunchKernelGGL((cvrp_decode_step_kernel<C::RL, C::EPL, C::V, C::OPT>), grid, dim3(256),
+                           shmem, s, B, (int)N, logits, lstride, mask_in, clip, temp, f.m.mode,
+                           action_in, action_out, logp_sel, seed, offset, status, epi);
+      });
 }

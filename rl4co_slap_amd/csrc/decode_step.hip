@@ -19,10 +19,10 @@ extern "C" int co_decode_step_ex(int64_t B, int64_t N, const float* logits, int6
     return CO_E_INVAL;
   // CO_DECODE_CERTIFIED changes only greedy picks' math (actions stay exact); other modes
   // and the filtered path run the exact math under it
-  const bool cert = (mode & CO_DECODE_CERTIFIED) != 0 && (mode & CO_DECODE_FAST) == 0;
-  const bool fast = (mode & CO_DECODE_FAST) != 0;
-  mode &= ~(CO_DECODE_FAST | CO_DECODE_CERTIFIED);
-  if (mode < 0 || mode > 2) return CO_E_MODE;
+  DecodeMode dm;
+  if (!dm.parse(mode)) return CO_E_MODE;
+  const bool cert = dm.cert, fast = dm.fast;
+  mode = dm.mode;
   if (B == 0) return CO_OK;
   if (!logits || !action_out) return CO_E_INVAL;
   if (mode == CO_DECODE_EVALUATE && !action_in) return CO_E_INVAL;
@@ -54,7 +54,7 @@ extern "C" int co_decode_step_ex(int64_t B, int64_t N, const float* logits, int6
                   logp_sel, full, status)
     switch (greedy_vw(N, lstride, logits, mask, mask, full)) {
       case 4: CO_ROW_DISPATCH(CO_GREEDY, 4); break;
-      case 2: CO_GREEDY(CO_RL16, 16 / CO_RL16, 2); break;  // N < 4
+      case 2: CO_ROW_CASE(CO_GREEDY, 2, 0); break;  // N < 4
       default: CO_ROW_DISPATCH(CO_GREEDY, 3);
     }
 #undef CO_GREEDY
