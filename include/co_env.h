@@ -576,6 +576,38 @@ int co_pomo_shared_baseline(int64_t instances, int64_t starts, const float* rewa
                             const float* log_likelihood, float* bl, float* max_reward,
                             int64_t* best_start, float* adv, float* loss_terms, void* stream);
 
+/* ------------------------------------------------ policy evaluation (rl4co/tasks/eval.py)
+ * The K-candidate evaluators (augmentations x starts x samples, eval.py:129-144,220-238,
+ * 278-301) score K*B action rows, unbatchify, take max(dim=1) and gather the winners.
+ * The candidate layout is batchify's repeat-major one: candidate k of instance b is row
+ * e = k*B + b (B = instances, K = candidates).
+ *
+ * Segmented best-of-K: best_idx[b] = the k whose reward[k*B + b] is largest (equal values,
+ * +0/-0 included: the lowest k; a NaN beats every number and the first NaN wins, as
+ * torch.max(dim) does); best_reward[b] = that value; best_actions[b, 0..T-1] (row-major,
+ * nullable) = that candidate's action row.  Action element (e, t) at
+ * actions[e*act_stride_b + t*act_stride_t].  best_actions must not alias actions; status
+ * is unused (the selection has no data-dependent failure) and may be NULL. */
+int co_best_of(int64_t instances, int64_t candidates, int64_t steps, const float* reward,
+               const int64_t* actions, int64_t act_stride_b, int64_t act_stride_t,
+               float* best_reward, int64_t* best_idx, int64_t* best_actions,
+               int32_t* status, void* stream);
+
+/* The same selection fused with TSPEnv.get_reward on the UN-replicated instances:
+ * locs f32 [instances, num_loc, 2]; every candidate row is a tour of T = num_loc steps
+ * (num_loc <= 1024, else CO_E_INVAL).  A candidate's reward is co_tsp_reward's: the
+ * negated f32 rounding of a double sum of the f32 edge lengths of the closed tour (the
+ * summation order is not fixed: a value may differ from co_tsp_reward's by one f32 ulp);
+ * the selection is exact on these values.  all_reward (nullable, f32 [K*B]) receives
+ * every candidate's reward.  check != 0: any candidate row that is not a permutation sets
+ * CO_ST_INVALID_TOUR (winner or not); an out-of-range index sets CO_ST_INDEX_RANGE as
+ * co_tsp_reward does.  best_actions (nullable, [instances, num_loc]) must not alias
+ * actions.  One launch: the instance's coordinates are read once for its K candidates. */
+int co_tsp_best_of(int64_t instances, int64_t num_loc, int64_t candidates, const float* locs,
+                   const int64_t* actions, int64_t act_stride_b, int64_t act_stride_t,
+                   int check, float* all_reward, float* best_reward, int64_t* best_idx,
+                   int64_t* best_actions, int32_t* status, void* stream);
+
 /* The deterministic part of SLAPGenerator._generate (slap/generator.py:51-81,137-155):
  * locs[B,L,2] aisle grid (x = aisle * inter_aisle_dist, y = loc * inter_loc_dist, products
  * in double rounded to f32), depot_loc_dist[B,L] and dist_mat[B,L,L] (nullable;

@@ -9,6 +9,9 @@ and ``rl4co.envs`` registry names.
 from . import _native
 from .envs import ENV_REGISTRY, CVRPEnv, SLAPEnv, TSPEnv, get_env
 from .td import TensorDict
+from .tasks import (AugmentationEval, EvalBase, GreedyEval, GreedyMultiStartAugmentEval,
+                    GreedyMultiStartEval, SamplingEval, evaluate_policy,
+                    get_automatic_batch_size)
 
 
 def check_errors(device="cuda") -> None:
@@ -26,4 +29,6 @@ def check_errors(device="cuda") -> None:
 
 
 __all__ = ["ENV_REGISTRY", "CVRPEnv", "SLAPEnv", "TSPEnv", "get_env", "TensorDict", "_native",
-           "check_errors"]
+           "check_errors", "AugmentationEval", "EvalBase", "GreedyEval",
+           "GreedyMultiStartAugmentEval", "GreedyMultiStartEval", "SamplingEval",
+           "evaluate_policy", "get_automatic_batch_size"]

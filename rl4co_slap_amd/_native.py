@@ -68,6 +68,8 @@ _SIGS = {
     "co_uniform_fill": [_p, _i64, _f32, _f32, _f32, _i32, _u64, _u64, _p],
     "co_randint_fill": [_p, _i64, _i64, _i64, _u64, _u64, _p],
     "co_pomo_shared_baseline": [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
+    "co_best_of": [_i64, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p, _p],
+    "co_tsp_best_of": [_i64, _i64, _i64, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p],
     "co_tsp_decode_step": [_i64, _i64, _p, _i64, _p, _f32, _f32, _i32, _p, _p, _p, _u64, _u64, _p,
                            _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p],
     "co_slap_decode_step": [_i64, _i64, _i64, _p, _i64, _p, _f32, _f32, _i32, _p, _p, _p, _u64,
@@ -165,7 +167,7 @@ HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt"
                 "co_cvrp_reset", "co_cvrp_step", "co_cvrp_action_mask", "co_cvrp_reward",
                 "co_cvrp_local_search",
                 "co_slap_reset", "co_slap_step", "co_slap_reward", "co_slap_local_search",
-                "co_gather_by_index",
+                "co_gather_by_index", "co_best_of", "co_tsp_best_of",
                 "co_decode_step"]
 
 

@@ -876,6 +876,71 @@ CO_HOST_API int co_gather_by_index(const void* src, int64_t outer, int64_t src_l
   return CO_OK;
 }
 
+// ------------------------------------------------------------------ policy evaluation
+// tasks/eval.py:137-144: unbatchify -> max(dim=1) -> gather_by_index over the [K, B] layout
+CO_HOST_API int co_best_of(int64_t B, int64_t K, int64_t T, const float* reward,
+                           const int64_t* actions, int64_t sb, int64_t st, float* best_reward,
+                           int64_t* best_idx, int64_t* best_actions, int32_t*, void*) {
+  if (B < 0 || K <= 0 || T < 0 || K > 0x7ffffffe) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!reward || !best_reward || !best_idx) return CO_E_INVAL;
+  if (T == 0) best_actions = nullptr;
+  if (best_actions && (!actions || best_actions == actions)) return CO_E_INVAL;
+  for (int64_t b = 0; b < B; ++b) {
+    float bv = reward[b];
+    int bk = 0;
+    for (int64_t k = 1; k < K; ++k)
+      if (argmax_better(reward[k * B + b], (int)k, bv, bk)) {
+        bv = reward[k * B + b];
+        bk = (int)k;
+      }
+    best_reward[b] = bv;
+    best_idx[b] = bk;
+    if (best_actions) {
+      const int64_t* src = actions + (bk * B + b) * sb;
+      for (int64_t t = 0; t < T; ++t) best_actions[b * T + t] = src[t * st];
+    }
+  }
+  return CO_OK;
+}
+
+// the same with every candidate scored as co_tsp_reward scores it, on the un-replicated locs
+CO_HOST_API int co_tsp_best_of(int64_t B, int64_t N, int64_t K, const float* locs,
+                               const int64_t* actions, int64_t sb, int64_t st, int check,
+                               float* all_reward, float* best_reward, int64_t* best_idx,
+                               int64_t* best_actions, int32_t* status, void*) {
+  if (B < 0 || N <= 0 || K <= 0 || N > 1024 || K > 0x7ffffffe || B > 0x7fffffff)
+    return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!locs || !actions || !best_reward || !best_idx || (check && !status)) return CO_E_INVAL;
+  if (best_actions == actions) return CO_E_INVAL;
+  if (reinterpret_cast<uintptr_t>(locs) & 7) return CO_E_ALIGN;
+  for (int64_t b = 0; b < B; ++b) {
+    float bv = 0.f;
+    int bk = -1;
+    for (int64_t k = 0; k < K; ++k) {
+      const int64_t e = k * B + b;
+      float r;
+      // one row against instance b: co_tsp_reward with the row's own base pointers
+      const int rc = co_tsp_reward(1, N, N, locs + b * N * 2, 1, actions + e * sb, sb, st, check,
+                                   &r, status, nullptr);
+      if (rc != CO_OK) return rc;
+      if (all_reward) all_reward[e] = r;
+      if (bk < 0 || argmax_better(r, (int)k, bv, bk)) {
+        bv = r;
+        bk = (int)k;
+      }
+    }
+    best_reward[b] = bv;
+    best_idx[b] = bk;
+    if (best_actions) {
+      const int64_t* src = actions + (bk * B + b) * sb;
+      for (int64_t t = 0; t < N; ++t) best_actions[b * N + t] = src[t * st];
+    }
+  }
+  return CO_OK;
+}
+
 // ---------------------------------------------------------------------------- decode
 // decoding.py:141-191 (tanh clip -> mask -> /T -> log_softmax), 327-399 (greedy argmax,
 // sampling by inverse CDF of a Philox draw keyed by (seed, offset, row), evaluate)

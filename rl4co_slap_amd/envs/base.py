@@ -148,6 +148,25 @@ class RL4COEnvBase(metaclass=abc.ABCMeta):
     def local_search(self, td, actions, **kwargs):
         raise NotImplementedError(f"Local is not implemented yet for {self.name} environment")
 
+    def best_of(self, td, actions, num_candidates, rewards=None):
+        """The best of ``num_candidates`` (K) action rows per instance: ``td`` holds the B
+        un-replicated instances, ``actions [K*B, T]`` the candidates in ``batchify``'s
+        repeat-major layout (row ``k*B + b``).  Returns ``(best_reward [B], best_idx [B],
+        best_actions [B, T])`` -- what the reference's evaluators compute with ``batchify``
+        -> ``get_reward`` -> ``unbatchify`` -> ``max(dim=1)`` -> ``gather_by_index``
+        (``rl4co/tasks/eval.py:137-144``).  ``num_candidates`` may be the reference's shape
+        tuple ``(num_augment, num_starts)``.  With ``rewards [K*B]`` given the rows are not
+        scored again (``ops.best_of``); else they are scored through the lazy multistart
+        td (no ``[K*B]`` copy of an entry the reward kernel reads in place)."""
+        from ..utils.ops import batchify, best_of
+
+        k = 1
+        for s in ([num_candidates] if isinstance(num_candidates, int) else num_candidates):
+            k *= s if s > 0 else 1
+        if rewards is None:
+            rewards = self.get_reward(batchify(td, k) if k > 1 else td, actions)
+        return best_of(rewards.reshape(-1), actions, k)
+
     @staticmethod
     def _instance_entries(td, keys):
         """The td entries under ``keys`` as a batched search reads them (an absent key gives

@@ -183,6 +183,57 @@ class TSPEnv(RL4COEnvBase):
         self.raise_for_status(status, msgs)
         return reward
 
+    # TSPEnv.best_of's dispatch (DESIGN.md section 4 has the measurements): co_tsp_best_of
+    # where it measured faster than reward + max + gather -- tours of more than 20 nodes
+    # whose K candidates fit one round of the kernel's block (K lane groups in 1024
+    # threads); elsewhere the two measured level and the composition stays.  True / False
+    # forces one side (tests, tools/bench_best_of.py).
+    _BEST_OF_MIN_LOC = 21
+    _BEST_OF_FORCE = None
+
+    def _best_of_fused(self, n: int, k: int) -> bool:
+        if self._BEST_OF_FORCE is not None:
+            return bool(self._BEST_OF_FORCE) and n <= 1024
+        lanes = 4 if n <= 32 else 8 if n <= 64 else 16 if n <= 128 else 32 if n <= 256 else 64
+        return self._BEST_OF_MIN_LOC <= n <= 1024 and k * lanes <= 1024
+
+    def best_of(self, td, actions, num_candidates, rewards=None):
+        """``RL4COEnvBase.best_of`` in one ``co_tsp_best_of`` launch: every candidate row
+        scored against its instance's un-replicated coordinates (read once for its K
+        candidates), the maximum taken and the winning row copied.  Applies when the rows
+        are tours of ``num_loc`` steps (``20 < num_loc <= 1024``) over ``td["locs"]``
+        ``[B, N, 2]`` and K fits one round of the kernel's block (``_best_of_fused``: e.g.
+        K <= 64 at TSP-100); otherwise (or with ``rewards`` given) the base composition
+        runs, which measured as fast there.
+        ``check_solution`` checks every candidate row, as ``get_reward`` does."""
+        k = 1
+        for s in ([num_candidates] if isinstance(num_candidates, int) else num_candidates):
+            k *= s if s > 0 else 1
+        raw = td.get_raw("locs") if hasattr(td, "get_raw") else td["locs"]
+        locs = raw.source() if isinstance(raw, RepeatedRows) else raw
+        if (rewards is not None or locs.dim() != 3 or actions.dim() != 2
+                or actions.shape[0] != k * locs.shape[0] or actions.shape[1] != locs.shape[1]
+                or locs.shape[0] == 0 or not self._best_of_fused(locs.shape[1], k)):
+            return super().best_of(td, actions, num_candidates, rewards)
+        nat.require_device(locs, actions)
+        locs = locs.contiguous().float()
+        if actions.dtype != torch.int64:
+            actions = actions.long()
+        b, n = locs.shape[0], locs.shape[1]
+        dev = locs.device
+        best_r = torch.empty(b, dtype=torch.float32, device=dev)
+        best_i = torch.empty(b, dtype=torch.int64, device=dev)
+        best_a = torch.empty((b, n), dtype=torch.int64, device=dev)
+        check = self.check_solution
+        status = self.status_word(dev)
+        nat.call("co_tsp_best_of", b, n, k, nat.ptr(locs), nat.ptr(actions), actions.stride(0),
+                 actions.stride(1), int(check), None, nat.ptr(best_r), nat.ptr(best_i),
+                 nat.ptr(best_a), nat.ptr(status), nat.stream_of(locs))
+        msgs = [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")] if check else []
+        msgs.append((nat.ST_INDEX_RANGE, RuntimeError, "index out of range in gather (actions)"))
+        self.raise_for_status(status, msgs)
+        return best_r, best_i, best_a
+
     def check_solution_validity(self, td, actions) -> None:
         """``tsp/env.py:165-173``."""
         self._get_reward(td, actions, check=True)

@@ -141,6 +141,53 @@ def unbatchify_and_gather(x: Tensor, idx: Tensor, n: int):
     return gather_by_index(x, idx, dim=idx.dim())
 
 
+def best_of(rewards: Tensor, actions: Tensor, num_candidates: int):
+    """The K-candidate evaluators' ``unbatchify`` -> ``max(dim=1)`` -> ``gather_by_index``
+    (``rl4co/tasks/eval.py:137-144``) in one ``co_best_of`` launch.  ``rewards [K*B]`` and
+    ``actions [K*B, T]`` (any strides, or None) are in ``batchify``'s repeat-major layout:
+    candidate ``k`` of instance ``b`` is row ``k*B + b``.  Returns ``(best_reward [B],
+    best_idx [B], best_actions [B, T])`` with ``torch.max``'s tie rule (the lowest ``k``;
+    the first NaN wins); ``best_actions`` is None without ``actions``."""
+    k = int(num_candidates)
+    if k <= 0 or rewards.dim() != 1 or rewards.shape[0] % k != 0:
+        raise ValueError(f"best_of: rewards of shape {tuple(rewards.shape)} do not hold "
+                         f"{num_candidates} candidates per instance")
+    if actions is not None and (actions.dim() != 2 or actions.shape[0] != rewards.shape[0]):
+        raise ValueError(f"best_of: actions of shape {tuple(actions.shape)} do not fit rewards "
+                         f"{tuple(rewards.shape)}")
+    nat.require_device(rewards, actions)
+    b = rewards.shape[0] // k
+    rewards = rewards.contiguous().float()
+    if actions is not None and actions.dtype != torch.int64:
+        actions = actions.long()
+    t = 0 if actions is None else actions.shape[1]
+    dev = rewards.device
+    best_r = torch.empty(b, dtype=torch.float32, device=dev)
+    best_i = torch.empty(b, dtype=torch.int64, device=dev)
+    best_a = None if actions is None else torch.empty((b, t), dtype=torch.int64, device=dev)
+    if b > 0:
+        sb, st = (0, 0) if actions is None else actions.stride()
+        nat.call("co_best_of", b, k, t, nat.ptr(rewards), nat.ptr(actions), sb, st,
+                 nat.ptr(best_r), nat.ptr(best_i), nat.ptr(best_a) if t > 0 else None, None,
+                 nat.stream_of(rewards))
+    return best_r, best_i, best_a
+
+
+def sample_n_random_actions(td, n: int):
+    """``ops.py:253-270``: ``n`` random feasible actions per instance, with replacement only
+    when an instance has fewer than ``n`` (the depot column excluded from the count, as the
+    reference does), flattened ``b n -> (n b)``.  Torch ops on the td's device (the
+    reference draws on the CPU and moves the result); the draw follows torch's generator of
+    that device and is not pinned."""
+    action_mask = td["action_mask"]
+    replace = bool(torch.sum(action_mask[:, 1:], 1).min() < n)
+    ps = torch.rand(action_mask.shape, device=action_mask.device)
+    ps[~action_mask] = -torch.inf
+    ps = torch.softmax(ps, dim=1)
+    selected = torch.multinomial(ps, n, replacement=replace)
+    return selected.t().reshape(-1)
+
+
 def get_distance(x: Tensor, y: Tensor):
     """``ops.py:88-90`` (elementwise helper, not on the timed path)."""
     return (x - y).norm(p=2, dim=-1)
