@@ -122,6 +122,50 @@ int co_tsp_two_opt(int64_t batch, int64_t num_loc, const float* locs, const floa
                    int64_t act_stride_t, int64_t max_iterations, int64_t* actions_out,
                    int32_t* sweeps_out, int32_t* status, void* stream);
 
+/* 2-opt + Or-opt descent on every row, the whole search of a row in one launch (the
+ * reference has 2-opt only; Or-opt is the classical "move a short chain elsewhere"
+ * companion).  The arguments are co_tsp_two_opt's plus `operators`, a mask of
+ * CO_TSP_LS_TWO_OPT | CO_TSP_LS_OR_OPT (0 or an unknown bit: CO_E_INVAL), and moves_out
+ * (nullable, int32 [batch, 2]): the applied 2-opt and the applied Or-opt moves per row.
+ * num_loc <= CO_TWO_OPT_MAX_N, exactly one of locs / distances, locs_batch, the action
+ * strides, actions_out not aliasing actions, the CO_E_* returns, the empty batch (a no-op)
+ * and the LDS staging of a matrix of n <= CO_TWO_OPT_STAGE_N are as co_tsp_two_opt has
+ * them, and D is the same: the given matrix (row = first operand) or the f32
+ * sqrt(dx*dx + dy*dy) of the coordinates.
+ *
+ * Or-opt neighbourhood.  The tour t has n cyclic positions.  A move is (L, i, k, rev):
+ * the segment t[i..i+L-1] of length L in {1, 2, 3}, 1 <= i and i+L-1 <= n-1 (position 0
+ * never moves, as in 2-opt), is taken out and reinserted -- reversed if rev = 1; L = 1 has
+ * rev = 0 only -- directly after node c = t[k], into the edge (t[k], t[(k+1)%n]) with
+ * 0 <= k <= n-1 and k not in [i-1, i+L-1].  With a = t[i-1], s1 = t[i], s2 = t[i+L-1],
+ * b = t[(i+L)%n], d = t[(k+1)%n] and (x, y) = (s1, s2) for rev = 0, (s2, s1) for rev = 1,
+ * the move is scored in f32, left to right, every operation rounded on its own (no FMA):
+ *   change = ((((D[a,b] + D[c,x]) + D[y,d]) - D[a,s1]) - D[s2,b]) - D[c,d]
+ * (as with 2-opt on an asymmetric matrix, the interior edges of a reversed segment are
+ * ignored: the formula is the definition).  An L without an admissible (i, k) -- n - L - 1
+ * < 1, or no i -- is skipped.
+ *
+ * Descent.  A sweep: if TWO_OPT is enabled, the 2-opt neighbourhood is scored exactly as
+ * in co_tsp_two_opt, the smallest change (equal values: the lexicographically first
+ * (i, j)) is taken and applied if (double)change < -1e-6.  If this sweep applied no 2-opt
+ * move and OR_OPT is enabled, the Or-opt neighbourhood is scored; the smallest change --
+ * on equal values the first in the order L ascending, then i, then k, then rev 0 before 1:
+ * a strict `<` against a running minimum that starts at 0 -- is applied if (double)change
+ * < -1e-6.  The search ends with the first sweep that applies nothing or after
+ * max_iterations sweeps; sweeps_out counts sweeps (one that scans both neighbourhoods
+ * counts once).  So with operators == CO_TSP_LS_TWO_OPT tours and sweeps are
+ * co_tsp_two_opt's, and with both bits the run starts with the 2-opt-only run.
+ * A row that is not a permutation (copied, 0 sweeps, CO_ST_INVALID_TOUR),
+ * max_iterations <= 0, n < 3 and the clamping of max_iterations are as in co_tsp_two_opt;
+ * such rows report 0 moves. */
+#define CO_TSP_LS_TWO_OPT 1
+#define CO_TSP_LS_OR_OPT 2
+int co_tsp_local_search(int64_t batch, int64_t num_loc, const float* locs,
+                        const float* distances, int64_t locs_batch, const int64_t* actions,
+                        int64_t act_stride_b, int64_t act_stride_t, int64_t max_iterations,
+                        int operators, int64_t* actions_out, int32_t* sweeps_out,
+                        int32_t* moves_out, int32_t* status, void* stream);
+
 /* ----------------------------------------------------------------- CVRP */
 
 /* CVRPEnv._reset + get_action_mask (cvrp/env.py:107-149).  N = customers.

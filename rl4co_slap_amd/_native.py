@@ -33,6 +33,8 @@ _SIGS = {
                               _i64, _p, _p, _p, _p],
     "co_tsp_reward": [_i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _p],
     "co_tsp_two_opt": [_i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _p],
+    "co_tsp_local_search": [_i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _p,
+                            _p],
     "co_cvrp_reset": [_i64, _i64, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _p, _p],
     "co_cvrp_step": [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "co_cvrp_action_mask": [_i64, _i64, _p, _p, _p, _p, _p, _p, _p],
@@ -98,6 +100,7 @@ DECODE_FAST = 0x100  # CO_DECODE_FAST mode flag (opt-in fast math; not bit-exact
 DECODE_CERTIFIED = 0x200  # CO_DECODE_CERTIFIED: fast math, greedy actions certified exact
 TWO_OPT_MAX_N = 1024  # CO_TWO_OPT_MAX_N: the longest tour co_tsp_two_opt takes
 TWO_OPT_STAGE_N = 126 # CO_TWO_OPT_STAGE_N: distance matrices up to this N are staged in LDS
+TSP_LS_TWO_OPT, TSP_LS_OR_OPT = 1, 2  # CO_TSP_LS_*: co_tsp_local_search's operator mask
 CVRP_LS_MAX_LEN = 1024  # CO_CVRP_LS_MAX_LEN: min(steps, 2*num_loc) + 1 may not exceed it
 CVRP_LS_STAGE_N = 117   # CO_CVRP_LS_STAGE_N: distance matrices up to this N are staged in LDS
 SLAP_LS_MAX_PRODUCTS = 128  # CO_SLAP_LS_MAX_PRODUCTS: the most products co_slap_local_search takes
@@ -163,7 +166,7 @@ HOST_LIB_PATH = os.path.join(_HERE, "_lib", "libco_env_host.so")
 _host = None
 # the host (CPU) library exports the env / decode subset of the C ABI (csrc/host)
 HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt",
-                "co_any_eq_i64",
+                "co_tsp_local_search", "co_any_eq_i64",
                 "co_cvrp_reset", "co_cvrp_step", "co_cvrp_action_mask", "co_cvrp_reward",
                 "co_cvrp_local_search",
                 "co_slap_reset", "co_slap_step", "co_slap_reward", "co_slap_local_search",

@@ -1,5 +1,5 @@
-// What the batched local searches share (two_opt.hip, cvrp_ls.hip, slap_ls.hip): only
-// pieces that at least two of them use.  Each kernel keeps its own admissibility test,
+// What the batched local searches share (two_opt.hip, tsp_ls.hip, cvrp_ls.hip, slap_ls.hip):
+// only pieces that at least two of them use.  Each kernel keeps its own admissibility test,
 // running minimum and move application; slap_ls.hip takes the bitmap and the entry-point
 // helpers alone.
 #pragma once

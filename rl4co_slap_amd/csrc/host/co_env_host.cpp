@@ -339,6 +339,111 @@ CO_HOST_API int co_tsp_two_opt(int64_t B, int64_t N, const float* locs, const fl
   return CO_OK;
 }
 
+// The 2-opt + Or-opt descent of include/co_env.h, as plain loops in the header's
+// enumeration order (2-opt: i, j; Or-opt: L, i, k, rev) with a strict `<` from 0, so equal
+// changes keep the first; every change is the header's left-to-right f32 expression.
+CO_HOST_API int co_tsp_local_search(int64_t B, int64_t N, const float* locs,
+                                    const float* distances, int64_t LB, const int64_t* actions,
+                                    int64_t sb, int64_t st, int64_t max_iterations,
+                                    int operators, int64_t* actions_out, int32_t* sweeps_out,
+                                    int32_t* moves_out, int32_t* status, void*) {
+  if (N <= 0 || N > CO_TWO_OPT_MAX_N) return CO_E_INVAL;
+  if (operators <= 0 || (operators & ~(CO_TSP_LS_TWO_OPT | CO_TSP_LS_OR_OPT))) return CO_E_INVAL;
+  const int rc = ls_check_args(B, LB, locs, distances,
+                               actions && actions_out && actions_out != actions && status);
+  if (rc != CO_OK || B == 0) return rc;
+  const int64_t n = N;
+  const int64_t max_it = ls_clamp_iterations(max_iterations);
+  std::vector<int64_t> tour((size_t)n), seg;
+  std::vector<uint8_t> seen((size_t)n);
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t* ar = actions + b * sb;
+    int64_t* out = actions_out + b * n;
+    std::fill(seen.begin(), seen.end(), 0);
+    bool bad = false;
+    for (int64_t k = 0; k < n; ++k) {
+      const int64_t a = ar[k * st];
+      out[k] = a;
+      tour[(size_t)k] = a;
+      if (a < 0 || a >= n || seen[(size_t)a]) bad = true;
+      else seen[(size_t)a] = 1;
+    }
+    if (sweeps_out) sweeps_out[b] = 0;
+    if (moves_out) moves_out[2 * b] = moves_out[2 * b + 1] = 0;
+    if (bad) {
+      set_status(status, CO_ST_INVALID_TOUR);
+      continue;
+    }
+    const LsDist D(locs, distances, b % LB, n);
+    auto t = [&](int64_t k) { return tour[(size_t)(k >= n ? k - n : k)]; };  // cyclic
+    int64_t it = 0;
+    int32_t n_two = 0, n_or = 0;
+    while (it < max_it) {
+      ++it;
+      if (operators & CO_TSP_LS_TWO_OPT) {
+        int64_t p = 0, q = 0;
+        float delta = 0.f;
+        for (int64_t i = 1; i < n - 1; ++i)
+          for (int64_t j = i + 1; j < n; ++j) {
+            const int64_t prev = t(i - 1), next = t(j + 1), ti = t(i), tj = t(j);
+            const float change = ((D(prev, tj) + D(ti, next)) - D(prev, ti)) - D(tj, next);
+            if (change < delta) {
+              p = i;
+              q = j;
+              delta = change;
+            }
+          }
+        if ((double)delta < -1e-6) {
+          std::reverse(tour.begin() + p, tour.begin() + q + 1);
+          ++n_two;
+          continue;
+        }
+      }
+      if (!(operators & CO_TSP_LS_OR_OPT)) break;
+      int64_t bl = 0, bi = 0, bk = 0, brev = 0;
+      float delta = 0.f;
+      for (int64_t L = 1; L <= 3; ++L) {
+        if (n - L - 1 < 1) continue;
+        for (int64_t i = 1; i + L - 1 <= n - 1; ++i) {
+          const int64_t a = t(i - 1), s1 = t(i), s2 = t(i + L - 1), nb = t(i + L);
+          for (int64_t k = 0; k < n; ++k) {
+            if (k >= i - 1 && k <= i + L - 1) continue;
+            const int64_t c = t(k), d = t(k + 1);
+            for (int64_t rev = 0; rev < (L > 1 ? 2 : 1); ++rev) {
+              const int64_t x = rev ? s2 : s1, y = rev ? s1 : s2;
+              const float change =
+                  ((((D(a, nb) + D(c, x)) + D(y, d)) - D(a, s1)) - D(s2, nb)) - D(c, d);
+              if (change < delta) {
+                bl = L;
+                bi = i;
+                bk = k;
+                brev = rev;
+                delta = change;
+              }
+            }
+          }
+        }
+      }
+      if (!((double)delta < -1e-6)) break;
+      // take the segment out, then put it back (reversed if asked) directly after node c
+      const int64_t c = t(bk);
+      seg.assign(tour.begin() + bi, tour.begin() + bi + bl);
+      if (brev) std::reverse(seg.begin(), seg.end());
+      tour.erase(tour.begin() + bi, tour.begin() + bi + bl);
+      const auto at = std::find(tour.begin(), tour.end(), c);
+      tour.insert(at + 1, seg.begin(), seg.end());
+      ++n_or;
+    }
+    for (int64_t k = 0; k < n; ++k) out[k] = tour[(size_t)k];
+    if (sweeps_out) sweeps_out[b] = (int32_t)it;
+    if (moves_out) {
+      moves_out[2 * b] = n_two;
+      moves_out[2 * b + 1] = n_or;
+    }
+  }
+  return CO_OK;
+}
+
 CO_HOST_API int co_any_eq_i64(const int64_t* x, int64_t n, int64_t value, int32_t* flag, void*) {
   if (n < 0 || !flag || (n > 0 && !x)) return CO_E_INVAL;
   int32_t f = 0;

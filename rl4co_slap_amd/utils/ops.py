@@ -294,6 +294,58 @@ def two_opt(actions: Tensor, locs: Tensor = None, distances: Tensor = None,
     return (out, sweeps) if return_sweeps else out
 
 
+_TSP_LS_OPERATORS = {"two_opt": nat.TSP_LS_TWO_OPT, "or_opt": nat.TSP_LS_OR_OPT}
+
+
+def tsp_local_search(actions: Tensor, locs: Tensor = None, distances: Tensor = None,
+                     operators=("two_opt", "or_opt"), max_iterations: int = 1000,
+                     return_sweeps: bool = False, return_moves: bool = False,
+                     status: Tensor = None):
+    """Best-improvement 2-opt + Or-opt descent on every row of ``actions [B, N]`` (any
+    strides, any integer dtype) on ``co_tsp_local_search``, the whole search in one launch
+    (``include/co_env.h`` states the Or-opt moves, the sweep and the tie rule).
+    ``operators`` names the enabled neighbourhoods (``"two_opt"``, ``"or_opt"``); the
+    distance source, the multistart layout, the result and the invalid-row behaviour are
+    ``two_opt``'s.  With ``return_sweeps`` the sweeps per row (int32 ``[B]``) and with
+    ``return_moves`` the applied (2-opt, Or-opt) moves per row (int32 ``[B, 2]``) follow the
+    tours, in that order."""
+    if isinstance(operators, str):
+        operators = (operators,)
+    operators = tuple(operators)
+    unknown = [o for o in operators if o not in _TSP_LS_OPERATORS]
+    if unknown or not operators:
+        raise ValueError(f"tsp_local_search: operators must be a non-empty choice of "
+                         f"{sorted(_TSP_LS_OPERATORS)}, got {operators!r}")
+    mask = 0
+    for o in operators:
+        mask |= _TSP_LS_OPERATORS[o]
+    src, which = _pick_source("tsp_local_search", locs, distances)
+    nat.require_device(actions, src)
+    if actions.dim() != 2:
+        raise ValueError(f"tsp_local_search: actions must be [B, N], got {tuple(actions.shape)}")
+    b, n = actions.shape
+    if n > nat.TWO_OPT_MAX_N:
+        raise ValueError(f"tsp_local_search: num_loc {n} exceeds the supported maximum "
+                         f"{nat.TWO_OPT_MAX_N}")
+    lb = src.shape[0] if src.dim() == 3 else 0
+    src, src_ptrs = _fit_source("tsp_local_search", src, which, lb, n, b,
+                                f"actions {tuple(actions.shape)}")
+    if actions.dtype != torch.int64:
+        actions = actions.long()
+    out, sweeps = _search_outputs((b, n), torch.int64, actions.device, return_sweeps)
+    moves = torch.empty((b, 2), dtype=torch.int32, device=actions.device) if return_moves else None
+    if b > 0 and n > 0:  # every row's counts are written
+        _run_with_status(lambda st: nat.call(
+            "co_tsp_local_search", b, n, *src_ptrs, lb, nat.ptr(actions), actions.stride(0),
+            actions.stride(1), int(max_iterations), mask, nat.ptr(out), nat.ptr(sweeps),
+            nat.ptr(moves), nat.ptr(st), nat.stream_of(actions)),
+            status, actions.device, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])
+    elif moves is not None:
+        moves.zero_()
+    res = (out,) +((sweeps,) if return_sweeps else ()) + ((moves,) if return_moves else ())
+    return res if len(res) > 1 else out
+
+
 def cvrp_local_search(actions: Tensor, demand: Tensor, locs: Tensor = None,
                       distances: Tensor = None, capacity: Tensor = None,
                       max_iterations: int = 1000, return_sweeps: bool = False,
