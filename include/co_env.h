@@ -498,7 +498,11 @@ int co_cvrp_decode_step(int64_t batch, int64_t num_loc, const float* logits,
  * (SURVEY.md 8d); they are the "policy" half of a rollout, not reference code.
  * TSP: step0 -> 0, then nearest unvisited to current_node (ties lowest index).
  * CVRP: nearest feasible customer, else depot.  SLAP: free location with the
- * lowest depot_loc_dist.  first_step != 0 selects the TSP step-0 branch. */
+ * lowest depot_loc_dist.  first_step != 0 selects the TSP step-0 branch, which reads
+ * none of locs / action_mask / current_node (they may be NULL then).  locs is read as
+ * (x, y) pairs and must be 8-byte aligned wherever it is read: CO_E_ALIGN otherwise, for
+ * all of co_tsp_nearest_action (first_step == 0), co_cvrp_nearest_action and
+ * co_cvrp_nearest_step. */
 int co_tsp_nearest_action(int64_t batch, int64_t num_loc, const float* locs,
                           const uint8_t* action_mask, const int64_t* current_node, int first_step,
                           int64_t* action_out, void* stream);

@@ -449,6 +449,8 @@ extern "C" int co_tsp_nearest_action(int64_t B, int64_t N, const float* locs,
   if (B < 0 || N <= 0) return CO_E_INVAL;
   if (B == 0) return CO_OK;
   if (!out || (!first_step && (!locs || !mask || !cur))) return CO_E_INVAL;
+  // the kernel reads locs as float2 (8-byte loads); the step-0 branch reads none of it
+  if (!first_step && (reinterpret_cast<uintptr_t>(locs) & 7)) return CO_E_ALIGN;
   hipLaunchKernelGGL(tsp_nearest_kernel, dim3(grid_for(B, 4, 256 * 32)), dim3(256), 0,
                      (hipStream_t)stream, B, (int)N, reinterpret_cast<const float2*>(locs), mask,
                      cur, first_step, out);
