@@ -166,6 +166,92 @@ int co_tsp_local_search(int64_t batch, int64_t num_loc, const float* locs,
                         int operators, int64_t* actions_out, int32_t* sweeps_out,
                         int32_t* moves_out, int32_t* status, void* stream);
 
+/* ------------------------------------------- TSP k-opt improvement MDP
+ * TSPkoptEnv (tsp/env.py:204-549) on ImprovementEnvBase (envs/common/base.py:336-403).
+ * A solution is a linked list rec (int64 [B, N]): rec[i] = j means edge i -> j; pred is the
+ * inverse of rec.  A valid rec is one N-cycle.  num_loc <= CO_KOPT_MAX_N and, where an
+ * action is given, 2 <= k_max <= CO_KOPT_MAX_K, else CO_E_INVAL; an empty batch is a no-op.
+ * D(a, c) is the f32 sqrt(dx*dx + dy*dy) of the coordinates (no FMA), locs f32
+ * [locs_batch, N, 2] with row b reading instance b % locs_batch, as co_tsp_reward.
+ * The cost of a row is sum over nodes i (not tour positions) of D(i, rec[i]), added in f64
+ * and rounded once to f32 as co_tsp_reward adds: a function of the (locs row, rec row) pair
+ * alone, so an unchanged rec has a bit-identical cost in every entry below.
+ * One wavefront per row, rec / positions / order in LDS; positions come from rec by
+ * pointer jumping (log2 N rounds). */
+#define CO_KOPT_MAX_N 1024
+#define CO_KOPT_MAX_K 16
+
+/* ImprovementEnvBase._get_linked_list_solution (base.py:386-393): rec[b, t[k]] =
+ * t[(k+1) % N] for the tour row t, element (b, k) at tour[b*stride_b + k*stride_t] (as
+ * co_tsp_reward's actions).  A row that is not a permutation of 0..N-1 sets
+ * CO_ST_INVALID_TOUR and is not written.  rec must not alias tour. */
+int co_tsp_linked_list(int64_t batch, int64_t num_loc, const int64_t* tour, int64_t stride_b,
+                       int64_t stride_t, int64_t* rec, int32_t* status, void* stream);
+
+/* ImprovementEnvBase._get_real_solution (base.py:371-384): solution[b] = the visiting
+ * order [0, rec[0], rec[rec[0]], ...] (int64 [B, N]).  A rec that is not one N-cycle sets
+ * CO_ST_INVALID_TOUR; the row is then not written. */
+int co_tsp_real_solution(int64_t batch, int64_t num_loc, const int64_t* rec, int64_t* solution,
+                         int32_t* status, void* stream);
+
+/* TSPkoptEnv._reset after the initial solution (tsp/env.py:304-331) and get_costs
+ * (base.py:361-369): cost[b] as defined above; visited_time (nullable, int64 [B, N]): the
+ * walk from node 0 gives rec[0] the value 1, the next node 2, ... and node 0 the value N.
+ * A rec that is not one N-cycle sets CO_ST_INVALID_TOUR; that row's outputs are
+ * unspecified (nothing is written out of bounds). */
+int co_tsp_kopt_reset(int64_t batch, int64_t num_loc, const float* locs, int64_t locs_batch,
+                      const int64_t* rec, float* cost, int64_t* visited_time, int32_t* status,
+                      void* stream);
+
+/* TSPkoptEnv._step (tsp/env.py:259-302).  With `action` (element (b, a) at
+ * action[b*act_stride_b + a*act_stride_a]): next_rec = operator(rec_in, action); with
+ * action == NULL (step_to_solution): next_rec = rec_in, k_max is unused and i is not
+ * touched.  Then
+ *   rec_out = next_rec (in place over rec_in allowed); cost_current = cost(next_rec);
+ *   cost_bsf_out = min(cost_current, cost_bsf_in) (in place allowed);
+ *   reward = cost_bsf_in - cost_bsf_out; rows with reward > 0 overwrite their rec_best row
+ *   (the reference mutates td["rec_best"] in place), the other rows of rec_best are left;
+ *   visited_time as co_tsp_kopt_reset's; i_out = i_in + 1 (in place allowed).
+ * Operator, k_max == 2 (DACT; action [B, 2] = (first, second), tsp/env.py:334-359): the
+ * path first -> ... -> second is reversed: rec[pred(first)] = second, rec[first] =
+ * rec_in[second] and every link inside the path turned round.  first == second changes
+ * nothing; second == pred(first) reverses the whole tour (rec[first] = second).
+ * Operator, k_max >= 3 (NeuOpt; action [B, 3*k_max] = index | left | right,
+ * tsp/env.py:361-390), the reference's walk: rec_next = rec_in with rec_next[left[j]] =
+ * right[j] for j = 0..k_max-1 in order (the last write wins); right_nodes =
+ * rec_in[index[.]]; cur = left[0]; N - 2 times: next = rec_next[cur]; if pred(next) != cur
+ * (pred of rec_in) and next is not in right_nodes: rec_next[next] = pred(next); cur = next.
+ * An action entry outside 0..N-1 sets CO_ST_INDEX_RANGE; a rec_in or a result that is not
+ * one N-cycle sets CO_ST_INVALID_TOUR; such a row's outputs are unspecified. */
+int co_tsp_kopt_step(int64_t batch, int64_t num_loc, int64_t k_max, const float* locs,
+                     int64_t locs_batch, const int64_t* rec_in, const int64_t* action,
+                     int64_t act_stride_b, int64_t act_stride_a, int64_t* rec_out,
+                     float* cost_current, const float* cost_bsf_in, float* cost_bsf_out,
+                     float* reward, int64_t* rec_best, int64_t* visited_time,
+                     const int64_t* i_in, int64_t* i_out, int32_t* status, void* stream);
+
+/* `steps` consecutive co_tsp_kopt_step calls with preset actions in one launch: action
+ * element (t, b, a) at actions[t*act_stride_t + b*act_stride_b + a*act_stride_a].  The
+ * state is updated in place: rec_current, cost_bsf, rec_best, i (nullable; += steps), and
+ * cost_current / visited_time are written for the last step (steps == 0: for the given
+ * rec).  reward [steps, B] receives every step's reward, cost_steps (nullable,
+ * [steps, B]) every step's cost_current.  Every output is bit-identical to the `steps`
+ * single calls.  On the device the row's state stays in LDS between the steps: per step
+ * the action is read and the reward written. */
+int co_tsp_kopt_steps(int64_t batch, int64_t num_loc, int64_t k_max, int64_t steps,
+                      const float* locs, int64_t locs_batch, const int64_t* actions,
+                      int64_t act_stride_t, int64_t act_stride_b, int64_t act_stride_a,
+                      int64_t* rec_current, float* cost_current, float* cost_bsf,
+                      int64_t* rec_best, int64_t* visited_time, int64_t* i, float* reward,
+                      float* cost_steps, int32_t* status, void* stream);
+
+/* TSPGenerator._get_initial_solutions, "greedy" (tsp/generator.py:82-94): the
+ * nearest-neighbour tour from node 0 as a linked list rec [B, N] (locs f32 [B, N, 2]).
+ * Each step goes to the node with the smallest f32 distance D, a visited node counting as
+ * 1e5 and the first minimum winning; the last node links back to 0. */
+int co_tsp_nearest_rec(int64_t batch, int64_t num_loc, const float* locs, int64_t* rec,
+                       void* stream);
+
 /* ----------------------------------------------------------------- CVRP */
 
 /* CVRPEnv._reset + get_action_mask (cvrp/env.py:107-149).  N = customers.

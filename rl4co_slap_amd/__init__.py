@@ -7,7 +7,8 @@ mask and reward functions, the autoregressive decode step and
 and ``rl4co.envs`` registry names.
 """
 from . import _native
-from .envs import ENV_REGISTRY, CVRPEnv, SLAPEnv, TSPEnv, get_env
+from .envs import (ENV_REGISTRY, IMPROVEMENT_ENV_REGISTRY, CVRPEnv, ImprovementEnvBase, SLAPEnv,
+                   TSPEnv, TSPkoptEnv, get_env)
 from .td import TensorDict
 from .tasks import (AugmentationEval, EvalBase, GreedyEval, GreedyMultiStartAugmentEval,
                     GreedyMultiStartEval, SamplingEval, evaluate_policy,
@@ -31,4 +32,5 @@ def check_errors(device="cuda") -> None:
 __all__ = ["ENV_REGISTRY", "CVRPEnv", "SLAPEnv", "TSPEnv", "get_env", "TensorDict", "_native",
            "check_errors", "AugmentationEval", "EvalBase", "GreedyEval",
            "GreedyMultiStartAugmentEval", "GreedyMultiStartEval", "SamplingEval",
-           "evaluate_policy", "get_automatic_batch_size"]
+           "evaluate_policy", "get_automatic_batch_size", "TSPkoptEnv", "ImprovementEnvBase",
+           "IMPROVEMENT_ENV_REGISTRY"]

@@ -35,6 +35,14 @@ _SIGS = {
     "co_tsp_two_opt": [_i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _p],
     "co_tsp_local_search": [_i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _p,
                             _p],
+    "co_tsp_linked_list": [_i64, _i64, _p, _i64, _i64, _p, _p, _p],
+    "co_tsp_real_solution": [_i64, _i64, _p, _p, _p, _p],
+    "co_tsp_kopt_reset": [_i64, _i64, _p, _i64, _p, _p, _p, _p, _p],
+    "co_tsp_kopt_step": [_i64, _i64, _i64, _p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p,
+                         _p, _p, _p, _p, _p],
+    "co_tsp_kopt_steps": [_i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _p,
+                          _p, _p, _p, _p, _p, _p],
+    "co_tsp_nearest_rec": [_i64, _i64, _p, _p, _p],
     "co_cvrp_reset": [_i64, _i64, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _p, _p],
     "co_cvrp_step": [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "co_cvrp_action_mask": [_i64, _i64, _p, _p, _p, _p, _p, _p, _p],
@@ -101,6 +109,7 @@ DECODE_CERTIFIED = 0x200  # CO_DECODE_CERTIFIED: fast math, greedy actions certi
 TWO_OPT_MAX_N = 1024  # CO_TWO_OPT_MAX_N: the longest tour co_tsp_two_opt takes
 TWO_OPT_STAGE_N = 126 # CO_TWO_OPT_STAGE_N: distance matrices up to this N are staged in LDS
 TSP_LS_TWO_OPT, TSP_LS_OR_OPT = 1, 2  # CO_TSP_LS_*: co_tsp_local_search's operator mask
+KOPT_MAX_N, KOPT_MAX_K = 1024, 16  # CO_KOPT_MAX_*: the k-opt entries' largest N and k_max
 CVRP_LS_MAX_LEN = 1024  # CO_CVRP_LS_MAX_LEN: min(steps, 2*num_loc) + 1 may not exceed it
 CVRP_LS_STAGE_N = 117   # CO_CVRP_LS_STAGE_N: distance matrices up to this N are staged in LDS
 SLAP_LS_MAX_PRODUCTS = 128  # CO_SLAP_LS_MAX_PRODUCTS: the most products co_slap_local_search takes
@@ -167,6 +176,8 @@ _host = None
 # the host (CPU) library exports the env / decode subset of the C ABI (csrc/host)
 HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt",
                 "co_tsp_local_search", "co_any_eq_i64",
+                "co_tsp_linked_list", "co_tsp_real_solution", "co_tsp_kopt_reset",
+                "co_tsp_kopt_step", "co_tsp_kopt_steps", "co_tsp_nearest_rec",
                 "co_cvrp_reset", "co_cvrp_step", "co_cvrp_action_mask", "co_cvrp_reward",
                 "co_cvrp_local_search",
                 "co_slap_reset", "co_slap_step", "co_slap_reward", "co_slap_local_search",

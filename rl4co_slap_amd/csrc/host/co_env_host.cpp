@@ -1119,6 +1119,251 @@ CO_HOST_API int co_decode_step(int64_t B, int64_t N, const float* logits, int64_
   return CO_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The k-opt improvement MDP of TSP (TSPkoptEnv, tsp/env.py:204-549; the header has the
+// semantics).  The operators follow the linked list directly -- pred and a walk -- where the
+// device works on positions, so the two builds check each other.
+namespace {
+
+inline bool kopt_sizes_ok(int64_t B, int64_t N) { return B >= 0 && N > 0 && N <= CO_KOPT_MAX_N; }
+
+// order = [0, rec[0], ...] and pos (its inverse) when rec is one N-cycle; false otherwise
+bool kopt_rank(const int64_t* rec, int64_t N, std::vector<int64_t>& order,
+               std::vector<int64_t>& pos) {
+  for (int64_t v = 0; v < N; ++v)
+    if (rec[v] < 0 || rec[v] >= N) return false;
+  std::fill(pos.begin(), pos.end(), -1);
+  int64_t cur = 0;
+  for (int64_t k = 0; k < N; ++k) {
+    if (pos[(size_t)cur] >= 0) return false;  // back at a node before all were seen
+    pos[(size_t)cur] = k;
+    order[(size_t)k] = cur;
+    cur = rec[cur];
+  }
+  return cur == 0;
+}
+
+float kopt_cost(const float* lr, const int64_t* rec, int64_t N) {
+  double acc = 0.0;
+  for (int64_t v = 0; v < N; ++v)
+    acc += (double)edge_len(lr[2 * v], lr[2 * v + 1], lr[2 * rec[v]], lr[2 * rec[v] + 1]);
+  return (float)acc;
+}
+
+// one row, one step on rec (valid on entry); false with the status bit set on a failure
+bool kopt_apply(int64_t N, int64_t K, const int64_t* act, int64_t sa, int64_t* rec,
+                std::vector<int64_t>& pred, std::vector<int64_t>& order,
+                std::vector<int64_t>& pos, int32_t* status) {
+  const int64_t A = K == 2 ? 2 : 3 * K;
+  for (int64_t j = 0; j < A; ++j)
+    if (act[j * sa] < 0 || act[j * sa] >= N) {
+      set_status(status, CO_ST_INDEX_RANGE);
+      return false;
+    }
+  for (int64_t v = 0; v < N; ++v) pred[(size_t)rec[v]] = v;
+  if (K == 2) {
+    const int64_t first = act[0], second = act[sa];
+    if (first == second) return true;
+    const int64_t before = pred[(size_t)first], after = rec[second];
+    const bool whole = before == second;
+    // turn the links of first -> ... -> second round (pred is of the old list)
+    for (int64_t cur = second; cur != first; cur = pred[(size_t)cur]) rec[cur] = pred[(size_t)cur];
+    rec[first] = whole ? second : after;
+    if (!whole) rec[before] = second;
+    return true;
+  }
+  int64_t right_nodes[CO_KOPT_MAX_K];
+  for (int64_t j = 0; j < K; ++j) right_nodes[j] = rec[act[j * sa]];
+  for (int64_t j = 0; j < K; ++j) rec[act[(K + j) * sa]] = act[(2 * K + j) * sa];
+  int64_t cur = act[K * sa];
+  for (int64_t it = 0; it < N - 2; ++it) {
+    const int64_t next = rec[cur], po = pred[(size_t)next];
+    bool right = false;
+    for (int64_t j = 0; j < K; ++j) right |= right_nodes[j] == next;
+    if (po != cur && !right) rec[next] = po;
+    cur = next;
+  }
+  if (!kopt_rank(rec, N, order, pos)) {
+    set_status(status, CO_ST_INVALID_TOUR);
+    return false;
+  }
+  return true;
+}
+
+// the shared body of reset / step / steps (the device's kopt_kernel, row by row)
+int kopt_rows(int64_t B, int64_t N, int64_t K, int64_t T, const float* locs, int64_t LB,
+              const int64_t* rec_in, int64_t* rec_out, const int64_t* actions, int64_t st,
+              int64_t sb, int64_t sa, float* cost_cur, const float* bsf_in, float* bsf_out,
+              float* reward, float* cost_steps, int64_t* rec_best, int64_t* vt,
+              const int64_t* i_in, int64_t* i_out, int32_t* status) {
+  std::vector<int64_t> rec((size_t)N), best((size_t)N), pred((size_t)N), order((size_t)N),
+      pos((size_t)N);
+  for (int64_t b = 0; b < B; ++b) {
+    const float* lr = locs + (b % LB) * N * 2;
+    std::copy(rec_in + b * N, rec_in + (b + 1) * N, rec.begin());
+    if (!kopt_rank(rec.data(), N, order, pos)) {
+      set_status(status, CO_ST_INVALID_TOUR);
+      continue;
+    }
+    float cost = kopt_cost(lr, rec.data(), N);
+    float bsf = bsf_in ? bsf_in[b] : 0.f;
+    bool dirty = false, stop = false;
+    for (int64_t t = 0; t < T; ++t) {
+      if (actions) {
+        if (!kopt_apply(N, K, actions + t * st + b * sb, sa, rec.data(), pred, order, pos,
+                        status)) {
+          stop = true;
+          break;
+        }
+        cost = kopt_cost(lr, rec.data(), N);
+      }
+      const float now = cost < bsf ? cost : bsf;
+      const float rew = bsf - now;
+      bsf = now;
+      if (rew > 0.0f) {
+        best = rec;
+        dirty = true;
+      }
+      reward[t * B + b] = rew;
+      if (cost_steps) cost_steps[t * B + b] = cost;
+    }
+    if (stop) continue;
+    if (rec_out) std::copy(rec.begin(), rec.end(), rec_out + b * N);
+    if (vt) {
+      kopt_rank(rec.data(), N, order, pos);
+      for (int64_t v = 0; v < N; ++v) vt[b * N + v] = v == 0 ? N : pos[(size_t)v];
+    }
+    if (dirty) std::copy(best.begin(), best.end(), rec_best + b * N);
+    cost_cur[b] = cost;
+    if (bsf_out) bsf_out[b] = bsf;
+    if (i_out) i_out[b] = i_in[b] + T;
+  }
+  return CO_OK;
+}
+
+}  // namespace
+
+CO_HOST_API int co_tsp_linked_list(int64_t B, int64_t N, const int64_t* tour, int64_t sb,
+                                   int64_t st, int64_t* rec, int32_t* status, void*) {
+  if (!kopt_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!tour || !rec || rec == tour || !status) return CO_E_INVAL;
+  std::vector<uint8_t> seen((size_t)N);
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t* tr = tour + b * sb;
+    std::fill(seen.begin(), seen.end(), 0);
+    bool bad = false;
+    for (int64_t k = 0; k < N && !bad; ++k) {
+      const int64_t x = tr[k * st];
+      if (x < 0 || x >= N || seen[(size_t)x]) bad = true;
+      else seen[(size_t)x] = 1;
+    }
+    if (bad) {
+      set_status(status, CO_ST_INVALID_TOUR);
+      continue;
+    }
+    for (int64_t k = 0; k < N; ++k) rec[b * N + tr[k * st]] = tr[(k + 1 == N ? 0 : k + 1) * st];
+  }
+  return CO_OK;
+}
+
+CO_HOST_API int co_tsp_real_solution(int64_t B, int64_t N, const int64_t* rec, int64_t* solution,
+                                     int32_t* status, void*) {
+  if (!kopt_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!rec || !solution || !status) return CO_E_INVAL;
+  std::vector<int64_t> order((size_t)N), pos((size_t)N);
+  for (int64_t b = 0; b < B; ++b) {
+    if (!kopt_rank(rec + b * N, N, order, pos)) {
+      set_status(status, CO_ST_INVALID_TOUR);
+      continue;
+    }
+    std::copy(order.begin(), order.end(), solution + b * N);
+  }
+  return CO_OK;
+}
+
+CO_HOST_API int co_tsp_kopt_reset(int64_t B, int64_t N, const float* locs, int64_t LB,
+                                  const int64_t* rec, float* cost, int64_t* visited_time,
+                                  int32_t* status, void*) {
+  if (!kopt_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (LB <= 0 || B % LB != 0) return CO_E_INVAL;
+  if (!locs || !rec || !cost || !status) return CO_E_INVAL;
+  if (reinterpret_cast<uintptr_t>(locs) & 7) return CO_E_ALIGN;
+  return kopt_rows(B, N, 0, 0, locs, LB, rec, nullptr, nullptr, 0, 0, 0, cost, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, visited_time, nullptr, nullptr, status);
+}
+
+CO_HOST_API int co_tsp_kopt_steps(int64_t B, int64_t N, int64_t k_max, int64_t steps,
+                                  const float* locs, int64_t LB, const int64_t* actions,
+                                  int64_t st, int64_t sb, int64_t sa, int64_t* rec_current,
+                                  float* cost_current, float* cost_bsf, int64_t* rec_best,
+                                  int64_t* visited_time, int64_t* i, float* reward,
+                                  float* cost_steps, int32_t* status, void*) {
+  if (!kopt_sizes_ok(B, N) || k_max < 2 || k_max > CO_KOPT_MAX_K || steps < 0)
+    return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (LB <= 0 || B % LB != 0) return CO_E_INVAL;
+  if (!locs || !rec_current || !cost_current || !cost_bsf || !rec_best ||
+      rec_best == rec_current || !visited_time || !status || (steps > 0 && (!actions || !reward)))
+    return CO_E_INVAL;
+  if (reinterpret_cast<uintptr_t>(locs) & 7) return CO_E_ALIGN;
+  return kopt_rows(B, N, k_max, steps, locs, LB, rec_current, rec_current, actions, st, sb, sa,
+                   cost_current, cost_bsf, cost_bsf, reward, cost_steps, rec_best, visited_time,
+                   i, i, status);
+}
+
+CO_HOST_API int co_tsp_kopt_step(int64_t B, int64_t N, int64_t k_max, const float* locs,
+                                 int64_t LB, const int64_t* rec_in, const int64_t* action,
+                                 int64_t sb, int64_t sa, int64_t* rec_out, float* cost_current,
+                                 const float* cost_bsf_in, float* cost_bsf_out, float* reward,
+                                 int64_t* rec_best, int64_t* visited_time, const int64_t* i_in,
+                                 int64_t* i_out, int32_t* status, void*) {
+  if (!kopt_sizes_ok(B, N) || (action && (k_max < 2 || k_max > CO_KOPT_MAX_K)))
+    return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (LB <= 0 || B % LB != 0) return CO_E_INVAL;
+  if (!locs || !rec_in || !rec_out || !cost_current || !cost_bsf_in || !cost_bsf_out ||
+      !reward || !rec_best || rec_best == rec_out || rec_best == rec_in || !visited_time ||
+      !status || (action && (!i_in || !i_out)))
+    return CO_E_INVAL;
+  if (reinterpret_cast<uintptr_t>(locs) & 7) return CO_E_ALIGN;
+  return kopt_rows(B, N, action ? k_max : 0, 1, locs, LB, rec_in, rec_out, action, 0, sb, sa,
+                   cost_current, cost_bsf_in, cost_bsf_out, reward, nullptr, rec_best,
+                   visited_time, action ? i_in : nullptr, action ? i_out : nullptr, status);
+}
+
+CO_HOST_API int co_tsp_nearest_rec(int64_t B, int64_t N, const float* locs, int64_t* rec, void*) {
+  if (!kopt_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!locs || !rec) return CO_E_INVAL;
+  if (reinterpret_cast<uintptr_t>(locs) & 7) return CO_E_ALIGN;
+  std::vector<uint8_t> seen((size_t)N);
+  for (int64_t b = 0; b < B; ++b) {
+    const float* lr = locs + b * N * 2;
+    int64_t* r = rec + b * N;
+    std::fill(r, r + N, 0);
+    std::fill(seen.begin(), seen.end(), 0);
+    seen[0] = 1;
+    int64_t cur = 0;
+    for (int64_t it = 0; it < N - 1; ++it) {
+      float best = INFINITY;
+      int64_t bi = -1;
+      for (int64_t v = 0; v < N; ++v) {
+        const float d = seen[(size_t)v] ? 1e5f
+                                        : edge_len(lr[2 * cur], lr[2 * cur + 1], lr[2 * v], lr[2 * v + 1]);
+        if (d < best) best = d, bi = v;
+      }
+      if (bi < 0) break;
+      r[cur] = bi;
+      seen[(size_t)bi] = 1;
+      cur = bi;
+    }
+  }
+  return CO_OK;
+}
+
 CO_HOST_API const char* co_build_info(void) {
   return "rl4co_slap_amd co_env: host (CPU) build of the env / decode entry points";
 }

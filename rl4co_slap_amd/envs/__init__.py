@@ -1,6 +1,8 @@
-"""Env registry (``rl4co/envs/__init__.py:38-83``) for the three hot-path envs.
+"""Env registry (``rl4co/envs/__init__.py:38-83``) for the three hot-path envs and the
+k-opt improvement env of TSP.
 
-Only ``tsp``, ``cvrp`` and ``slap`` are built MI355X-native; asking for any other
+Only ``tsp``, ``cvrp`` and ``slap`` (constructive, ``ENV_REGISTRY``) and ``tsp_kopt``
+(improvement, ``IMPROVEMENT_ENV_REGISTRY``) are built MI355X-native; asking for any other
 reference env raises the reference's ``ValueError``.
 """
 from .base import RL4COEnvBase
@@ -8,12 +10,14 @@ from .common import Generator, get_sampler
 from .cvrp import CVRPEnv, CVRPGenerator
 from .slap import SLAPEnv, SLAPGenerator
 from .tsp import TSPEnv, TSPGenerator
+from .tsp_kopt import ImprovementEnvBase, TSPkoptEnv
 
 ENV_REGISTRY = {"cvrp": CVRPEnv, "tsp": TSPEnv, "slap": SLAPEnv}
+IMPROVEMENT_ENV_REGISTRY = {"tsp_kopt": TSPkoptEnv}
 
 
 def get_env(env_name: str, *args, **kwargs) -> RL4COEnvBase:
-    env_cls = ENV_REGISTRY.get(env_name, None)
+    env_cls = ENV_REGISTRY.get(env_name, None) or IMPROVEMENT_ENV_REGISTRY.get(env_name, None)
     if env_cls is None:
         raise ValueError(
             f"Unknown environment {env_name}. Available environments: {ENV_REGISTRY.keys()}")
@@ -21,4 +25,5 @@ def get_env(env_name: str, *args, **kwargs) -> RL4COEnvBase:
 
 
 __all__ = ["RL4COEnvBase", "Generator", "get_sampler", "TSPEnv", "TSPGenerator", "CVRPEnv",
-           "CVRPGenerator", "SLAPEnv", "SLAPGenerator", "ENV_REGISTRY", "get_env"]
+           "CVRPGenerator", "SLAPEnv", "SLAPGenerator", "ENV_REGISTRY", "get_env",
+           "ImprovementEnvBase", "TSPkoptEnv", "IMPROVEMENT_ENV_REGISTRY"]

@@ -34,6 +34,27 @@ class TSPGenerator(Generator):
             locs = self.loc_sampler.sample(shape)
         return TensorDict({"locs": locs}, batch_size=batch_size)
 
+    def _get_initial_solutions(self, coordinates) -> torch.Tensor:
+        """``tsp/generator.py:62-99`` (the improvement MDP's start): a linked list ``rec``
+        ``[B, N]`` on the coordinates' device.  ``"random"``: the tour
+        ``torch.rand(B, N).argsort()`` from the global CPU RNG -- the reference's draw, so
+        the same seed gives the same ``rec`` -- linked by ``co_tsp_linked_list``;
+        ``"greedy"``: the nearest-neighbour tour from node 0 (``co_tsp_nearest_rec``)."""
+        b = coordinates.shape[0]
+        if self.init_sol_type == "random":
+            from .tsp_kopt import ImprovementEnvBase
+
+            tour = torch.rand(b, self.num_loc).argsort().long()
+            return ImprovementEnvBase._get_linked_list_solution(tour.to(coordinates.device))
+        if self.init_sol_type == "greedy":
+            nat.require_device(coordinates)
+            locs = coordinates.float().contiguous()
+            rec = torch.empty((b, self.num_loc), dtype=torch.int64, device=locs.device)
+            nat.call("co_tsp_nearest_rec", b, self.num_loc, nat.ptr(locs), nat.ptr(rec),
+                     nat.stream_of(locs))
+            return rec
+        raise NotImplementedError()
+
 
 class TSPEnv(RL4COEnvBase):
     """``tsp/env.py:29-173`` with ``_step``/``_reset``/``get_reward`` on the device."""
