@@ -20,7 +20,7 @@ LIB = os.path.join(OUT_DIR, "libco_env.so")
 SOURCES = ["tsp.hip", "cvrp.hip", "slap.hip", "ops.hip", "decode_step.hip", "decode_tsp.hip",
            "decode_env.hip",
            "rollout.hip",
-           "nearest.hip", "two_opt.hip", "tsp_ls.hip", "cvrp_ls.hip", "slap_ls.hip", "best_of.hip",
+           "nearest.hip", "tsp_ls.hip", "cvrp_ls.hip", "slap_ls.hip", "best_of.hip",
            "tsp_kopt.hip"]
 HEADERS = ["co_common.hpp", "co_tile.hpp", "co_math.hpp", "co_diag.hpp", "decode_common.hpp",
            "decode_fused.hpp", "co_local_search.hpp"]

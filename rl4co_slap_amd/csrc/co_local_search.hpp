@@ -1,4 +1,4 @@
-// What the batched local searches share (two_opt.hip, tsp_ls.hip, cvrp_ls.hip, slap_ls.hip):
+// What the batched local searches share (tsp_ls.hip, cvrp_ls.hip, slap_ls.hip):
 // only pieces that at least two of them use.  Each kernel keeps its own admissibility test,
 // running minimum and move application; slap_ls.hip takes the bitmap and the entry-point
 // helpers alone.
@@ -15,7 +15,7 @@ constexpr int kStep = 63;  // strip positions a window advances by (64 lanes, on
 
 // ---------------------------------------------------------------------------
 // The diagonal strip of the 2-opt moves (i, j), 1 <= i < j <= n-1, of a cyclic tour of n
-// positions (two_opt.hip describes the walk; cvrp_ls.hip walks it too).  Element c of strip
+// positions (tsp_ls.hip describes the walk; cvrp_ls.hip walks it too).  Element c of strip
 // row q (0 <= c <= n): row q holds diagonal r = q + 1 (n - r elements, the closing one
 // included) and then diagonal n-1-r (r + 1 elements).  An odd middle diagonal (n-1)/2 ends
 // the strip as the first part of a last, half-filled row.  j == n marks a closing element.
@@ -95,6 +95,14 @@ __device__ __forceinline__ TwoOptCandidate two_opt_candidate(const StripCursor& 
   cand.j = m.j;
   cand.mine = live & (lane < kStep) & (m.j < n);
   return cand;
+}
+
+// The wave's best candidate from every lane's running (change, key) minimum, equal changes
+// going to the lower key; the result is wave-uniform (scalar registers).
+__device__ __forceinline__ void wave_best_move(float& best, int& bkey) {
+  grp_argmin_split<64>(best, bkey);
+  best = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(best)));
+  bkey = __builtin_amdgcn_readfirstlane(bkey);
 }
 
 // Reverse positions p..r of every array of the pack (the wave's 64 lanes share the swaps).

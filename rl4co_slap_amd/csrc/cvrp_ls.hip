@@ -2,7 +2,7 @@
 // for gfx950: best-improvement 2-opt + relocate under an exact integer capacity test.
 // include/co_env.h states the search; tests/cvrp_ls_ref.py restates it in numpy.
 //
-// Layout: as two_opt.hip, one wavefront (a 64-thread workgroup) owns one row for its whole
+// Layout: as tsp_ls.hip, one wavefront (a 64-thread workgroup) owns one row for its whole
 // search.  LDS holds, per tour position k (slots = min(T, 2N) + 2: the longest giant tour
 // plus the sentinel position m = position 0):
 //   g[k]     the node                    P[k]  its coordinates (coordinate path only)
@@ -24,7 +24,7 @@
 //
 // A sweep walks two strips in windows of 64 positions that overlap by one (lanes 0..62 own
 // a candidate each, lane 63 only feeds lane 62), one distance per candidate:
-//  - the 2-opt moves along diagonals, exactly two_opt.hip's strip (n = m);
+//  - the 2-opt moves along diagonals, exactly tsp_ls.hip's strip (n = m);
 //  - the relocate candidates row by row: row i holds j = 0..m-1 and a closing element
 //    j = m.  D[c, g[j+1]] is the next element's D[g[j+1], c] on the coordinate path (the
 //    same dx*dx + dy*dy), taken from the next lane; a matrix may be asymmetric, so the
@@ -241,9 +241,7 @@ __global__ __launch_bounds__(64) void cvrp_ls_kernel(
         }
         cur.advance();
       }
-      grp_argmin_split<64>(best, bkey);
-      best = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(best)));
-      bkey = __builtin_amdgcn_readfirstlane(bkey);
+      wave_best_move(best, bkey);
       ++it;
       if (!((double)best < -1e-6)) break;  // nothing applied: the search ends
       const int p = (bkey >> 16) & 0x3fff, r = bkey & 0xffff;

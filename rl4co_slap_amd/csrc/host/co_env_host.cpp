@@ -277,66 +277,16 @@ CO_HOST_API int co_tsp_reward(int64_t B, int64_t N, int64_t T, const float* locs
 
 // tsp/env.py:192-197 -> tsp/local_search.py:14-74: best-improvement 2-opt, the reference's
 // scalar double loop per row (one move per sweep; strict `<` from delta = 0 in ascending
-// (i, j) order, so equal changes keep the first; the -1e-6 tests in double)
+// (i, j) order, so equal changes keep the first; the -1e-6 tests in double): the descent
+// below with the 2-opt neighbourhood alone.  The reference skips a move when
+// `prev == tour[j] || next == tour[i]`; on a permutation with 1 <= i < j <= n-1 that never
+// holds, so the shared loop has no such test.
 CO_HOST_API int co_tsp_two_opt(int64_t B, int64_t N, const float* locs, const float* distances,
                                int64_t LB, const int64_t* actions, int64_t sb, int64_t st,
                                int64_t max_iterations, int64_t* actions_out,
-                               int32_t* sweeps_out, int32_t* status, void*) {
-  if (N <= 0 || N > CO_TWO_OPT_MAX_N) return CO_E_INVAL;
-  const int rc = ls_check_args(B, LB, locs, distances,
-                               actions && actions_out && actions_out != actions && status);
-  if (rc != CO_OK || B == 0) return rc;
-  const int64_t n = N;
-  const int64_t max_it = ls_clamp_iterations(max_iterations);
-  std::vector<int64_t> tour((size_t)n);
-  std::vector<uint8_t> seen((size_t)n);
-  for (int64_t b = 0; b < B; ++b) {
-    const int64_t* ar = actions + b * sb;
-    int64_t* out = actions_out + b * n;
-    std::fill(seen.begin(), seen.end(), 0);
-    bool bad = false;
-    for (int64_t k = 0; k < n; ++k) {
-      const int64_t a = ar[k * st];
-      out[k] = a;
-      tour[(size_t)k] = a;
-      if (a < 0 || a >= n || seen[(size_t)a]) bad = true;
-      else seen[(size_t)a] = 1;
-    }
-    if (sweeps_out) sweeps_out[b] = 0;
-    if (bad) {
-      set_status(status, CO_ST_INVALID_TOUR);
-      continue;
-    }
-    const LsDist D(locs, distances, b % LB, n);
-    double min_change = -1.0;
-    int64_t it = 0;
-    while (min_change < -1e-6 && it < max_it) {
-      int64_t p = 0, q = 0;
-      float delta = 0.f;
-      for (int64_t i = 1; i < n - 1; ++i)
-        for (int64_t j = i + 1; j < n; ++j) {
-          const int64_t prev = tour[(size_t)(i - 1)], next = tour[(size_t)((j + 1) % n)];
-          const int64_t ti = tour[(size_t)i], tj = tour[(size_t)j];
-          if (prev == tj || next == ti) continue;
-          const float change = ((D(prev, tj) + D(ti, next)) - D(prev, ti)) - D(tj, next);
-          if (change < delta) {
-            p = i;
-            q = j;
-            delta = change;
-          }
-        }
-      if ((double)delta < -1e-6) {
-        std::reverse(tour.begin() + p, tour.begin() + q + 1);
-        min_change = (double)delta;
-      } else {
-        min_change = 0.0;
-      }
-      ++it;
-    }
-    for (int64_t k = 0; k < n; ++k) out[k] = tour[(size_t)k];
-    if (sweeps_out) sweeps_out[b] = (int32_t)it;
-  }
-  return CO_OK;
+                               int32_t* sweeps_out, int32_t* status, void* stream) {
+  return co_tsp_local_search(B, N, locs, distances, LB, actions, sb, st, max_iterations,
+                             CO_TSP_LS_TWO_OPT, actions_out, sweeps_out, nullptr, status, stream);
 }
 
 // The 2-opt + Or-opt descent of include/co_env.h, as plain loops in the header's

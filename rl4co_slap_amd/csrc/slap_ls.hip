@@ -2,7 +2,7 @@
 // gfx950: best-improvement move-to-free-slot + product swap on the exact integer QAP
 // objective.  include/co_env.h states the search; tests/slap_ls_ref.py restates it in numpy.
 //
-// Layout: as two_opt.hip and cvrp_ls.hip, one wavefront (a 64-thread workgroup) owns one row
+// Layout: as tsp_ls.hip and cvrp_ls.hip, one wavefront (a 64-thread workgroup) owns one row
 // for its whole search.  LDS holds
 //   W[a][c]  the flow counts, uint16 (W <= O * (K / 2) <= 32768), rows padded to an even
 //            length and built from the picklist with 32-bit LDS adds of 1 << 16 * (c & 1)

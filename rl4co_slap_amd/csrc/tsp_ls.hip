@@ -1,15 +1,38 @@
-// Batched 2-opt + Or-opt descent for TSP tours (co_tsp_local_search; TSPEnv.local_search
-// with operators=...) for gfx950.  include/co_env.h states the moves, the f32 scoring order
-// and the tie rule; two_opt.hip describes the LDS-resident tour state and the 2-opt strip,
-// which this kernel walks through the same two_opt_candidate.
+// Batched best-improvement local search for TSP tours for gfx950: 2-opt alone
+// (co_tsp_two_opt; TSPEnv.local_search, tsp/env.py:192-197 -> tsp/local_search.py:14-74) and
+// the 2-opt + Or-opt descent (co_tsp_local_search; TSPEnv.local_search with operators=...).
+// include/co_env.h states the moves, the f32 scoring order and the tie rule.  Both entry
+// points launch one kernel template; OR_OPT = false compiles the Or-opt half and its LDS
+// array out and is what a 2-opt-only search runs.
 //
-// Layout: one wavefront (a 64-thread workgroup) owns one row for its whole search.  LDS
-// holds the tour (n + 1: the sentinel tour[n] = tour[0]), the edge terms
-//   E[k] = D[tour[k-1], tour[k]]   (k = 0: the closing edge)
-// the per-segment joining edge A[i] = D[tour[i-1], tour[i+L]] of the segment length L being
-// scanned, and the distance source: the coordinates in tour order P, or the staged matrix
-// (n <= CO_TWO_OPT_STAGE_N: 4n^2 + 12(n+1) + 12 bytes <= 64 KiB), or nothing (matrix through
-// L2).
+// Layout: one wavefront (a 64-thread workgroup) owns one row for its whole search -- all
+// sweeps, the wave-wide argmin, the move and the termination test run inside the one
+// launch.  LDS holds the tour (n + 1: the sentinel tour[n] = tour[0]), the per-position
+// edge term
+//   E[k] = D[tour[k-1], tour[k]]   (k = 0: the closing edge D[tour[n-1], tour[0]])
+// with OR_OPT the per-segment joining edge A[i] = D[tour[i-1], tour[i+L]] of the segment
+// length L being scanned, and the distance source in tour order: the coordinates
+// P[k] = locs[tour[k]] (a candidate then touches tour positions only), or the instance's
+// distance matrix when it fits (n <= CO_TWO_OPT_STAGE_N: 4n^2 + the state's 8(n+1) bytes,
+// with A 12(n+1) + 12, <= 64 KiB); a larger matrix is read through L2.  The two subtracted
+// operands of a 2-opt move's `change` are E[i] and E[j+1]: the same f32 values the
+// reference recomputes, so `change` is bit-identical.
+//
+// The 2-opt sweep scores the (n-1)(n-2)/2 moves (i, j), 1 <= i < j <= n-1.  Along a
+// diagonal (i+1, j+1 follows i, j) the second added term of a move, D[t[i], t[j+1]], is the
+// first added term of its successor, so every lane evaluates ONE distance
+// g = D[t[i-1], t[j]] (one sqrt, or one matrix gather) and takes the other from the next
+// lane.  The diagonals are laid end to end in a strip: diagonal d = j - i holds its n-1-d
+// moves and then one closing element (j = n, read through the sentinels tour[n] = tour[0],
+// P[n] = P[0]) that only supplies the last move's second term.  Diagonal r is followed by
+// diagonal n-1-r, so each such pair is n+1 elements long and strip position x maps to
+// (i, j) with one division by n+1 -- done once per lane, then advanced by the wave's step.
+// The wave walks the strip in windows of 64 positions that overlap by one: lanes 0..62 own
+// a move each, lane 63 only feeds lane 62.  Each lane keeps a running (change, i<<16 | j)
+// minimum, equal changes going to the lower key (the reference's ascending scan with a
+// strict `<`); one wave reduction with the same rule gives the sweep's move.  After the
+// reversal of tour[i..j] (and P[i..j]) only E[i..j+1] is recomputed, in the new (row,
+// column) orientation.
 //
 // The Or-opt scan.  For one L the candidates (i, k, rev) form a table of n - L rows
 // (i = 1 .. n-L) by n columns (k = 0 .. n-1).  Of a candidate's six terms, E[i], E[i+L]
@@ -39,12 +62,17 @@ using namespace co;
 
 namespace {
 
-// bytes of tour + E + A, rounded so that P (float2) and the staged matrix start 16-aligned
-__host__ __device__ constexpr int ls_state_bytes(int n) { return (12 * (n + 1) + 15) & ~15; }
+// bytes of tour + E, and with or_opt of A too, then rounded so that P (float2) and the
+// staged matrix start 16-aligned
+__host__ __device__ constexpr int ls_state_bytes(int n, bool or_opt) {
+  return or_opt ? (12 * (n + 1) + 15) & ~15 : 8 * (n + 1);
+}
 
-static_assert(4 * CO_TWO_OPT_STAGE_N * CO_TWO_OPT_STAGE_N + ls_state_bytes(CO_TWO_OPT_STAGE_N) <=
-                  64 * 1024,
-              "a staged matrix with the tour, edge terms and joining edges must fit 64 KiB");
+static_assert(4 * CO_TWO_OPT_STAGE_N * CO_TWO_OPT_STAGE_N +
+                      ls_state_bytes(CO_TWO_OPT_STAGE_N, true) <= 64 * 1024,
+              "a staged matrix with the tour, edge terms and joining edges (the larger of the "
+              "two states) must fit 64 KiB of LDS");
+static_assert(CO_TWO_OPT_MAX_N < (1 << 15), "2-opt move keys pack j <= n into 16 bits");
 static_assert(CO_TWO_OPT_MAX_N <= 1024, "Or-opt keys pack i and k into 10 bits each");
 
 // key of an Or-opt candidate: ascending in the enumeration order L, i, k, rev
@@ -52,25 +80,31 @@ __device__ __forceinline__ int or_key(int L, int i, int k, int rev) {
   return (((L << 10 | i) << 10 | k) << 1) | rev;
 }
 
-template <int MODE>
+// OR_OPT = false: 2-opt alone -- `ops` is not read and there is no A.
+template <int MODE, bool OR_OPT>
 __global__ __launch_bounds__(64) void tsp_ls_kernel(
     int64_t B, int n, const float* __restrict__ src, int64_t LB,
     const int64_t* __restrict__ actions, int64_t sb, int64_t st, int max_it, int ops,
     int64_t* __restrict__ out, int32_t* __restrict__ sweeps, int32_t* __restrict__ moves,
     int32_t* status) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  unsigned char* s_src = s_raw + ls_state_bytes(n, OR_OPT);  // the staged distance source
   int* tour = reinterpret_cast<int*>(s_raw);                  // n + 1 (sentinel)
   float* E = reinterpret_cast<float*>(s_raw + 4 * (n + 1));   // n (+ 1 of padding)
-  float* A = reinterpret_cast<float*>(s_raw + 8 * (n + 1));   // n + 1
+  [[maybe_unused]] float* A = reinterpret_cast<float*>(s_raw + 8 * (n + 1));  // OR_OPT: n + 1
   uint32_t* bits = reinterpret_cast<uint32_t*>(E);  // the permutation bitmap, before E is built
-  [[maybe_unused]] float2* P = reinterpret_cast<float2*>(s_raw + ls_state_bytes(n));  // n + 1
-  [[maybe_unused]] float* Dl = reinterpret_cast<float*>(s_raw + ls_state_bytes(n));   // n * n
+  [[maybe_unused]] float2* P = reinterpret_cast<float2*>(s_src);  // kCoords: n + 1
+  [[maybe_unused]] float* Dl = reinterpret_cast<float*>(s_src);   // kMatLds: n * n
   const int lane = threadIdx.x;
-  const int total2 = (n - 2) * (n + 1) / 2;  // the 2-opt strip (two_opt.hip)
+  const int total2 = (n - 2) * (n + 1) / 2;  // the 2-opt strip, in rows of n + 1
   const StripCursor start(lane, n + 1);      // both strips have rows of n + 1
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     const int64_t* arow = actions + b * sb;
     int64_t* orow = out + b * (int64_t)n;
+    // here, not after the row check: the scalar 64-bit remainder is where SGPR use peaks,
+    // and after the check it puts the staged-matrix 2-opt instance past the 100 SGPRs that 8
+    // waves per SIMD allow
+    const int64_t inst = LB == B ? b : b % LB;
     __syncthreads();  // the previous row's LDS reads are done
     for (int k = lane; k < ((n + 31) >> 5); k += 64) bits[k] = 0;
     __syncthreads();
@@ -88,12 +122,12 @@ __global__ __launch_bounds__(64) void tsp_ls_kernel(
     if (bad || n < 3 || max_it <= 0) {  // wave-uniform: the row is copied
       if (bad && lane == 0) set_status(status, CO_ST_INVALID_TOUR);
       for (int k = lane; k < n; k += 64) orow[k] = arow[(int64_t)k * st];
+      // n < 3: the reference's one sweep finds no candidate
       if (sweeps && lane == 0) sweeps[b] = (!bad && max_it > 0) ? 1 : 0;
       if (moves && lane < 2) moves[2 * b + lane] = 0;
       continue;
     }
     __syncthreads();
-    const int64_t inst = LB == B ? b : b % LB;
     [[maybe_unused]] const float* Dg = src + inst * (int64_t)n * n;  // the matrix modes
     if (lane == 0) tour[n] = tour[0];
     if constexpr (MODE == kCoords) {
@@ -110,10 +144,12 @@ __global__ __launch_bounds__(64) void tsp_ls_kernel(
     int it = 0, n_two = 0, n_or = 0;
     while (it < max_it) {
       ++it;
-      if (ops & CO_TSP_LS_TWO_OPT) {  // the sweep of two_opt.hip
-        float best = 0.f;
+      if (!OR_OPT || (ops & CO_TSP_LS_TWO_OPT)) {
+        float best = 0.f;  // the reference's delta = 0 with a strict `<`
         int bkey = 0x7fffffff;
         StripCursor cur = start;
+        // every lane runs every window (the lane exchange needs the whole wave); the strip's
+        // last element is a closing one, so the last move is at total2 - 2
         for (int x0 = 0; x0 < total2 - 1; x0 += kStep) {
           const TwoOptCandidate m = two_opt_candidate(cur, x0 + lane < total2, lane, n, E, dist);
           const bool take =
@@ -122,9 +158,7 @@ __global__ __launch_bounds__(64) void tsp_ls_kernel(
           bkey = take ? m.key : bkey;
           cur.advance();
         }
-        grp_argmin_split<64>(best, bkey);
-        best = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(best)));
-        bkey = __builtin_amdgcn_readfirstlane(bkey);
+        wave_best_move(best, bkey);
         if ((double)best < -1e-6) {
           const int p = bkey >> 16, r = bkey & 0xffff;  // reverse tour[p..r]
           if constexpr (MODE == kCoords) reverse_segment(lane, p, r, tour, P);
@@ -139,7 +173,7 @@ __global__ __launch_bounds__(64) void tsp_ls_kernel(
           continue;
         }
       }
-      if (!(ops & CO_TSP_LS_OR_OPT)) break;
+      if (!OR_OPT || !(ops & CO_TSP_LS_OR_OPT)) break;  // min_change = 0: the search ends
       float best = 0.f;
       int bkey = 0x7fffffff;
       for (int L = 1; L <= 3 && n - L - 1 >= 1; ++L) {
@@ -177,9 +211,7 @@ __global__ __launch_bounds__(64) void tsp_ls_kernel(
         }
         __syncthreads();  // A is rewritten for the next L
       }
-      grp_argmin_split<64>(best, bkey);
-      best = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(best)));
-      bkey = __builtin_amdgcn_readfirstlane(bkey);
+      wave_best_move(best, bkey);
       if (!((double)best < -1e-6)) break;  // neither neighbourhood improves: the search ends
       const int rev = bkey & 1, k = (bkey >> 1) & 1023, i = (bkey >> 11) & 1023, L = bkey >> 21;
       // the segment, in its new order, in lanes 0 .. L-1
@@ -230,23 +262,18 @@ __global__ __launch_bounds__(64) void tsp_ls_kernel(
     }
     for (int k = lane; k < n; k += 64) orow[k] = tour[k];
     if (sweeps && lane == 0) sweeps[b] = it;
-    if (moves && lane == 0) {
-      moves[2 * b] = n_two;
-      moves[2 * b + 1] = n_or;
-    }
+    if (moves && lane < 2) moves[2 * b + lane] = lane ? n_or : n_two;
   }
 }
 
-}  // namespace
-
-extern "C" int co_tsp_local_search(int64_t B, int64_t N, const float* locs,
-                                   const float* distances, int64_t locs_batch,
-                                   const int64_t* actions, int64_t sb, int64_t st,
-                                   int64_t max_iterations, int operators, int64_t* actions_out,
-                                   int32_t* sweeps_out, int32_t* moves_out, int32_t* status,
-                                   void* stream) {
+// The checks and the launch of both entry points; `operators` is a valid mask (with
+// OR_OPT = false it is CO_TSP_LS_TWO_OPT and the kernel does not read it).
+template <bool OR_OPT>
+int launch_tsp_ls(int64_t B, int64_t N, const float* locs, const float* distances,
+                  int64_t locs_batch, const int64_t* actions, int64_t sb, int64_t st,
+                  int64_t max_iterations, int operators, int64_t* actions_out,
+                  int32_t* sweeps_out, int32_t* moves_out, int32_t* status, void* stream) {
   if (N <= 0 || N > CO_TWO_OPT_MAX_N) return CO_E_INVAL;
-  if (operators <= 0 || (operators & ~(CO_TSP_LS_TWO_OPT | CO_TSP_LS_OR_OPT))) return CO_E_INVAL;
   const int rc = check_search_args(
       B, locs_batch, locs, distances,
       actions && actions_out && actions_out != actions && status, true);
@@ -254,14 +281,36 @@ extern "C" int co_tsp_local_search(int64_t B, int64_t N, const float* locs,
   const int n = (int)N, max_it = clamp_iterations(max_iterations);
   const dim3 grid = row_grid(B);
   hipStream_t s = (hipStream_t)stream;
-  const int state = ls_state_bytes(n);
+  const int state = ls_state_bytes(n, OR_OPT);
 #define CO_TSP_LS(MODE, SRC, LDS)                                                               \
-  hipLaunchKernelGGL(tsp_ls_kernel<MODE>, grid, dim3(64), (size_t)(LDS), s, B, n, SRC,          \
-                     locs_batch, actions, sb, st, max_it, operators, actions_out, sweeps_out,   \
-                     moves_out, status)
+  hipLaunchKernelGGL((tsp_ls_kernel<MODE, OR_OPT>), grid, dim3(64), (size_t)(LDS), s, B, n,     \
+                     SRC, locs_batch, actions, sb, st, max_it, operators, actions_out,          \
+                     sweeps_out, moves_out, status)
   if (locs) CO_TSP_LS(kCoords, locs, state + 8 * (n + 1));
   else if (n <= CO_TWO_OPT_STAGE_N) CO_TSP_LS(kMatLds, distances, state + 4 * n * n);
   else CO_TSP_LS(kMatGlobal, distances, state);
 #undef CO_TSP_LS
   return launch_status();
+}
+
+}  // namespace
+
+extern "C" int co_tsp_two_opt(int64_t B, int64_t N, const float* locs, const float* distances,
+                              int64_t locs_batch, const int64_t* actions, int64_t sb, int64_t st,
+                              int64_t max_iterations, int64_t* actions_out, int32_t* sweeps_out,
+                              int32_t* status, void* stream) {
+  return launch_tsp_ls<false>(B, N, locs, distances, locs_batch, actions, sb, st, max_iterations,
+                              CO_TSP_LS_TWO_OPT, actions_out, sweeps_out, nullptr, status, stream);
+}
+
+extern "C" int co_tsp_local_search(int64_t B, int64_t N, const float* locs,
+                                   const float* distances, int64_t locs_batch,
+                                   const int64_t* actions, int64_t sb, int64_t st,
+                                   int64_t max_iterations, int operators, int64_t* actions_out,
+                                   int32_t* sweeps_out, int32_t* moves_out, int32_t* status,
+                                   void* stream) {
+  if (operators <= 0 || (operators & ~(CO_TSP_LS_TWO_OPT | CO_TSP_LS_OR_OPT))) return CO_E_INVAL;
+  const auto launch = operators == CO_TSP_LS_TWO_OPT ? launch_tsp_ls<false> : launch_tsp_ls<true>;
+  return launch(B, N, locs, distances, locs_batch, actions, sb, st, max_iterations, operators,
+                actions_out, sweeps_out, moves_out, status, stream);
 }

@@ -262,27 +262,22 @@ class TSPEnv(RL4COEnvBase):
     def local_search(self, td, actions, max_iterations: int = 1000, *,
                      return_sweeps: bool = False, operators=("two_opt",)):
         """``tsp/env.py:192-197`` (``tsp/local_search.py:14-74``): best-improvement 2-opt on
-        every row of ``actions`` in one ``co_tsp_two_opt`` launch, on ``td["distances"]``
+        every row of ``actions`` in one ``co_tsp_local_search`` launch
+        (``ops.tsp_local_search``), on ``td["distances"]``
         when present, else the Euclidean distances of ``td["locs"]`` (a multistart td's
         un-replicated ``locs`` read in place, as ``_get_reward`` does).  Returns int64
         ``[B, N]`` on the actions' device; with ``return_sweeps`` also the sweeps per row.
         A row that is not a permutation raises ``AssertionError("Invalid tour")`` (the
-        reference does not check).  Any other ``operators`` -- ``("two_opt", "or_opt")``
-        adds the Or-opt neighbourhood -- runs the descent of ``co_tsp_local_search``
-        (``ops.tsp_local_search``)."""
-        from ..utils.ops import tsp_local_search, two_opt
+        reference does not check).  ``operators=("two_opt", "or_opt")`` adds the Or-opt
+        neighbourhood to the descent."""
+        from ..utils.ops import tsp_local_search
 
         dist, = self._instance_entries(td, ["distances"])
         locs, = self._instance_entries(td, ["locs"]) if dist is None else (None,)
         status = self.status_word(actions.device)
-        if operators == "two_opt" or tuple(operators) == ("two_opt",):
-            res = two_opt(actions, locs=locs, distances=dist,
-                          max_iterations=max_iterations, return_sweeps=return_sweeps,
-                          status=status)
-        else:
-            res = tsp_local_search(actions, locs=locs, distances=dist, operators=operators,
-                                   max_iterations=max_iterations,
-                                   return_sweeps=return_sweeps, status=status)
+        res = tsp_local_search(actions, locs=locs, distances=dist, operators=operators,
+                               max_iterations=max_iterations, return_sweeps=return_sweeps,
+                               status=status)
         self.raise_for_status(status, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])
         return res
 

@@ -271,27 +271,44 @@ def two_opt(actions: Tensor, locs: Tensor = None, distances: Tensor = None,
     with ``return_sweeps`` also the sweeps executed per row (int32 ``[B]``).  A row that is
     not a permutation raises ``AssertionError("Invalid tour")`` -- or, with a caller-held
     ``status`` word, sets ``ST_INVALID_TOUR`` there and the caller reads it."""
-    src, which = _pick_source("two_opt", locs, distances)
+    return _tsp_search("two_opt", None, actions, locs, distances, max_iterations,
+                       return_sweeps, False, status)
+
+
+def _tsp_search(name, mask, actions, locs, distances, max_iterations, return_sweeps,
+                return_moves, status):
+    """What ``two_opt`` (``mask`` None: the ``co_tsp_two_opt`` symbol) and
+    ``tsp_local_search`` (``co_tsp_local_search`` with the operator ``mask``) share; ``name``
+    is the caller's, for the messages."""
+    src, which = _pick_source(name, locs, distances)
     nat.require_device(actions, src)
     if actions.dim() != 2:
-        raise ValueError(f"two_opt: actions must be [B, N], got {tuple(actions.shape)}")
+        raise ValueError(f"{name}: actions must be [B, N], got {tuple(actions.shape)}")
     b, n = actions.shape
     if n > nat.TWO_OPT_MAX_N:
-        raise ValueError(f"two_opt: num_loc {n} exceeds the supported maximum "
+        raise ValueError(f"{name}: num_loc {n} exceeds the supported maximum "
                          f"{nat.TWO_OPT_MAX_N}")
     lb = src.shape[0] if src.dim() == 3 else 0
-    src, src_ptrs = _fit_source("two_opt", src, which, lb, n, b,
-                                f"actions {tuple(actions.shape)}")
+    src, src_ptrs = _fit_source(name, src, which, lb, n, b, f"actions {tuple(actions.shape)}")
     if actions.dtype != torch.int64:
         actions = actions.long()
     out, sweeps = _search_outputs((b, n), torch.int64, actions.device, return_sweeps)
-    if b > 0 and n > 0:
-        _run_with_status(lambda st: nat.call(
-            "co_tsp_two_opt", b, n, *src_ptrs, lb, nat.ptr(actions), actions.stride(0),
-            actions.stride(1), int(max_iterations), nat.ptr(out), nat.ptr(sweeps), nat.ptr(st),
-            nat.stream_of(actions)),
+    moves = torch.empty((b, 2), dtype=torch.int32, device=actions.device) if return_moves else None
+    if b > 0 and n > 0:  # every row's counts are written
+        args = (b, n, *src_ptrs, lb, nat.ptr(actions), actions.stride(0), actions.stride(1),
+                int(max_iterations))
+        if mask is None:
+            symbol, args = "co_tsp_two_opt", args + (nat.ptr(out), nat.ptr(sweeps))
+        else:
+            symbol = "co_tsp_local_search"
+            args += (mask, nat.ptr(out), nat.ptr(sweeps), nat.ptr(moves))
+        _run_with_status(
+            lambda st: nat.call(symbol, *args, nat.ptr(st), nat.stream_of(actions)),
             status, actions.device, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])
-    return (out, sweeps) if return_sweeps else out
+    elif moves is not None:
+        moves.zero_()
+    res = (out,) + ((sweeps,) if return_sweeps else ()) + ((moves,) if return_moves else ())
+    return res if len(res) > 1 else out
 
 
 _TSP_LS_OPERATORS = {"two_opt": nat.TSP_LS_TWO_OPT, "or_opt": nat.TSP_LS_OR_OPT}
@@ -319,31 +336,8 @@ def tsp_local_search(actions: Tensor, locs: Tensor = None, distances: Tensor = N
     mask = 0
     for o in operators:
         mask |= _TSP_LS_OPERATORS[o]
-    src, which = _pick_source("tsp_local_search", locs, distances)
-    nat.require_device(actions, src)
-    if actions.dim() != 2:
-        raise ValueError(f"tsp_local_search: actions must be [B, N], got {tuple(actions.shape)}")
-    b, n = actions.shape
-    if n > nat.TWO_OPT_MAX_N:
-        raise ValueError(f"tsp_local_search: num_loc {n} exceeds the supported maximum "
-                         f"{nat.TWO_OPT_MAX_N}")
-    lb = src.shape[0] if src.dim() == 3 else 0
-    src, src_ptrs = _fit_source("tsp_local_search", src, which, lb, n, b,
-                                f"actions {tuple(actions.shape)}")
-    if actions.dtype != torch.int64:
-        actions = actions.long()
-    out, sweeps = _search_outputs((b, n), torch.int64, actions.device, return_sweeps)
-    moves = torch.empty((b, 2), dtype=torch.int32, device=actions.device) if return_moves else None
-    if b > 0 and n > 0:  # every row's counts are written
-        _run_with_status(lambda st: nat.call(
-            "co_tsp_local_search", b, n, *src_ptrs, lb, nat.ptr(actions), actions.stride(0),
-            actions.stride(1), int(max_iterations), mask, nat.ptr(out), nat.ptr(sweeps),
-            nat.ptr(moves), nat.ptr(st), nat.stream_of(actions)),
-            status, actions.device, [(nat.ST_INVALID_TOUR, AssertionError, "Invalid tour")])
-    elif moves is not None:
-        moves.zero_()
-    res = (out,) +((sweeps,) if return_sweeps else ()) + ((moves,) if return_moves else ())
-    return res if len(res) > 1 else out
+    return _tsp_search("tsp_local_search", mask, actions, locs, distances, max_iterations,
+                       return_sweeps, return_moves, status)
 
 
 def cvrp_local_search(actions: Tensor, demand: Tensor, locs: Tensor = None,

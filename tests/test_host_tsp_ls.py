@@ -163,6 +163,45 @@ def test_two_opt_mask_equals_co_tsp_two_opt():
         assert (got[2][:, 1] == 0).all()
 
 
+@pytest.mark.parametrize("b,n", lc.TWO_OPT_ONLY_COORDS)
+def test_two_opt_only_counts_moves_on_coordinates(b, n):
+    locs, *case = lc.uniform_case(b, n, TWO_OPT, 1000, None, 0.0)
+    lc.check_two_opt_only(ops, case, "cpu", locs=locs)
+
+
+@pytest.mark.parametrize("b,n", lc.TWO_OPT_ONLY_MATRICES)
+def test_two_opt_only_counts_moves_on_distances(b, n):
+    D, *case = lc.matrix_case(b, n, TWO_OPT, 1000, 0.0)
+    lc.check_two_opt_only(ops, case, "cpu", distances=D)
+
+
+def test_two_opt_only_counts_moves_on_asymmetric_matrices():
+    """{1, 2, 3} matrices under a cap of 50 (such a search may cycle): every sweep applies a
+    move but a last one that finds none, which only a row stopped by the cap can lack."""
+    D, *case, _ = lc.int_matrix_case(8, 14, False, TWO_OPT, 50)
+    sweeps, moves = lc.check_two_opt_only(ops, case, "cpu", 50, distances=D)
+    assert ((moves[:, 0] == sweeps - 1) | ((sweeps == 50) & (moves[:, 0] == sweeps))).all()
+
+
+@pytest.mark.parametrize("max_it", [0, 1, 3])
+def test_two_opt_only_max_iterations(max_it):
+    locs, *case = lc.uniform_case(16, 20, TWO_OPT, max_it, None, 0.0)
+    sweeps, moves = lc.check_two_opt_only(ops, case, "cpu", max_it, locs=locs)
+    # a random 20-city tour is not 2-optimal after three moves: every row stops at the cap,
+    # having applied a move in each sweep
+    assert (sweeps == max_it).all() and np.array_equal(moves[:, 0], sweeps)
+    if max_it == 0:
+        assert np.array_equal(case[1], case[0])
+
+
+def test_two_opt_only_invalid_rows():
+    lc.check_two_opt_only_invalid_rows(ops, "cpu", nat.ST_INVALID_TOUR)
+
+
+def test_two_opt_only_null_outputs():
+    lc.check_two_opt_only_null_outputs(ops, "cpu")
+
+
 def test_both_operators_start_with_the_two_opt_run():
     locs, tours, ref, sweeps, moves = lc.uniform_case(16, 20)
     _, _, ref2, sweeps2 = tc.uniform_case(16, 20)

@@ -1,6 +1,7 @@
-"""Inputs and restatement results shared by the co_tsp_local_search tests
-(tests/test_host_tsp_ls.py on the host build, tests/test_gpu_tsp_ls.py on the device): each
-case is built and solved by tests/tsp_ls_ref.py once per session and handed out read-only.
+"""Inputs and restatement results shared by the TSP local-search tests (co_tsp_local_search:
+tests/test_host_tsp_ls.py on the host build, tests/test_gpu_tsp_ls.py on the device;
+co_tsp_two_opt takes the TWO_OPT cases through the view in tests/two_opt_cases.py): each case
+is built and solved by tests/tsp_ls_ref.py once per session and handed out read-only.
 
 A case meant to exercise Or-opt after 2-opt must apply at least one Or-opt move in a
 quarter of its rows (``min_or_rows``, asserted when the case is built; the seeds are
@@ -9,14 +10,23 @@ with OR_OPT alone from random tours, where Or-opt moves are plentiful."""
 import functools
 
 import numpy as np
+import torch
 
 from ls_cases_common import frozen, to_device, to_numpy
 from tsp_ls_ref import OR_OPT, TWO_OPT, local_search
-from two_opt_cases import perms, uniform_locs
 from two_opt_ref import dist_from_locs
 
 BOTH = TWO_OPT | OR_OPT
 NAMES = {TWO_OPT: ("two_opt",), OR_OPT: ("or_opt",), BOTH: ("two_opt", "or_opt")}
+
+
+def perms(b, n, seed):
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.permutation(n) for _ in range(b)]).astype(np.int64).reshape(b, n)
+
+
+def uniform_locs(b, n, seed):
+    return np.random.default_rng(seed + 1000).random((b, n, 2), dtype=np.float32)
 
 
 def solve(D, tours, operators=BOTH, max_iterations=1000, min_or_rows=0.0):
@@ -111,6 +121,62 @@ KNOWN = [
     ("n = 4", np.array([(0, 0), (1, 0), (1, 1), (0, 1)], dtype=np.float32), None, OR_OPT,
      [0, 2, 1, 3], [0, 1, 2, 3], 2, (0, 1)),
 ]
+
+
+# ``ops.tsp_local_search(..., operators=("two_opt",))`` with both counts asked for: on the
+# device the kernel instance without the Or-opt half, which co_tsp_two_opt runs with a null
+# moves_out.  (b, n): the sizes around 3 (nothing to move below), one and several windows of
+# 64, and on the distances path both sides of the LDS staging cut (126).
+TWO_OPT_ONLY_COORDS = [(9, 1), (9, 2), (9, 3), (37, 5), (16, 20), (8, 63), (8, 64), (8, 65)]
+TWO_OPT_ONLY_MATRICES = [(8, 12), (2, 126), (2, 127)]
+
+
+def check_two_opt_only(ops, case, device, max_iterations=1000, **src):
+    """``case`` = (tours, restatement tours, sweeps, moves) of the TWO_OPT restatement: the
+    tours and sweeps are ``ops.two_opt``'s and the restatement's, no Or-opt move is counted
+    and the 2-opt count is the restatement's.  Returns the restatement's (sweeps, moves)."""
+    tours, ref, sweeps, moves = case
+    got = run(ops.tsp_local_search, tours, device=device, operators=TWO_OPT,
+              max_iterations=max_iterations, **src)
+    old = to_numpy(ops.two_opt(to_device(tours, np.int64, device), return_sweeps=True,
+                               max_iterations=max_iterations,
+                               **{k: to_device(v, np.float32, device) for k, v in src.items()}))
+    assert np.array_equal(got[0], old[0]) and np.array_equal(got[0], ref), "tours differ"
+    assert np.array_equal(got[1], old[1]) and np.array_equal(got[1], sweeps), (got[1], sweeps)
+    assert (got[2][:, 1] == 0).all() and (moves[:, 1] == 0).all()
+    assert np.array_equal(got[2][:, 0], moves[:, 0]), ("moves differ", got[2][:, 0], moves[:, 0])
+    return sweeps, moves
+
+
+def check_two_opt_only_invalid_rows(ops, device, status_bit):
+    """One duplicate and one out-of-range row at (16, 20): the status bit is set, both rows
+    are copied with 0 sweeps and 0 moves, every other row is the restatement's."""
+    locs, tours, ref, sweeps, moves = uniform_case(16, 20, TWO_OPT, 1000, None, 0.0)
+    bad = tours.copy()
+    bad[3, 7] = bad[3, 8]
+    bad[5, 0] = 20
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    out, sw, mv = to_numpy(ops.tsp_local_search(
+        to_device(bad, np.int64, device), locs=to_device(locs, np.float32, device),
+        operators=("two_opt",), return_sweeps=True, return_moves=True, status=status))
+    assert int(status.item()) == status_bit
+    keep = ~np.isin(np.arange(16), [3, 5])
+    assert np.array_equal(out[keep], ref[keep]) and np.array_equal(sw[keep], sweeps[keep])
+    assert np.array_equal(mv[keep], moves[keep])
+    assert np.array_equal(out[~keep], bad[~keep])
+    assert (sw[~keep] == 0).all() and (mv[~keep] == 0).all()
+
+
+def check_two_opt_only_null_outputs(ops, device):
+    """moves_out null with sweeps_out given, and the reverse: what is given is still right."""
+    locs, tours, ref, sweeps, moves = uniform_case(16, 20, TWO_OPT, 1000, None, 0.0)
+    t, l = to_device(tours, np.int64, device), to_device(locs, np.float32, device)
+    out, sw = to_numpy(ops.tsp_local_search(t, locs=l, operators=("two_opt",),
+                                            return_sweeps=True))
+    assert np.array_equal(out, ref) and np.array_equal(sw, sweeps)
+    out, mv = to_numpy(ops.tsp_local_search(t, locs=l, operators=("two_opt",),
+                                            return_moves=True))
+    assert np.array_equal(out, ref) and np.array_equal(mv, moves)
 
 
 def run(fn, tours, locs=None, distances=None, device="cpu", operators=BOTH, **kw):

@@ -2,10 +2,11 @@
 B = 8,192 and TSP-20 at B = 65,536, from random permutations and from nearest-neighbour
 tours (measurement tool, not part of the product).  Per case, ms per call (tools/ls_bench.py:
 the median of 5 calls after a warm-up, by device events around the call) of
-co_tsp_two_opt, of the new entry with TWO_OPT only and of co_tsp_two_opt again (old / new /
-old: the spread of the two old runs is what the new figure is read against), then of the
-new entry with both operators; the mean tour length after each, the sweeps and the applied
-moves.  The host build runs both operators on the first 256 rows and is compared.
+co_tsp_two_opt, of co_tsp_local_search with TWO_OPT only and of co_tsp_two_opt again (the two
+entries run the same kernel instance: the spread of the two co_tsp_two_opt runs is what
+any figure of this tool is read against), then of co_tsp_local_search with both operators;
+the mean tour length after each, the sweeps and the applied moves.  The host build runs
+both operators on the first 256 rows and is compared.
 Usage: python tools/bench_tsp_ls.py [--quick] -> one JSON line."""
 import json
 import os
