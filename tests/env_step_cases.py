@@ -106,7 +106,9 @@ tests/test_host_env_step_cases.py asserts that every path listed here has a case
   tsp.hip   tsp_nearest_kernel (co_tsp_nearest_action)     test_tsp_nearest_action[*]
   tsp.hip   tsp_reward_kernel<4>   co_tsp_reward when neither T == N <= 1024 row-major nor
     the step-major T == N <= 256 route applies   test_tsp_reward_generic[*]
-  (co_tsp_step's kernels are pinned by test_tsp_step_kernel_paths_vs_reference.)
+  (co_tsp_step's kernels -- tsp_step_group_kernel<2 .. 64> and tsp_step_kernel -- and the
+  K-steps-per-launch entries co_tsp_steps and co_slap_closest_steps have their table in
+  tests/steps_cases.py.)
 """
 import collections
 import functools

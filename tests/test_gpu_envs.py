@@ -12,6 +12,7 @@ from oracle.envs import (CVRPOracle, SLAPOracle, TSPOracle, cvrp_nearest_action,
                          slap_closest_free_action, tsp_nearest_action)
 from oracle.td import TD
 from rl4co_slap_amd.envs import CVRPEnv, SLAPEnv, TSPEnv
+from steps_cases import TSP_STEP_N
 
 pytestmark = pytest.mark.gpu
 
@@ -562,14 +563,17 @@ def test_slap_reward_paths_vs_oracle(dev, b, l, p, o, k):
     assert st & 8
 
 
-@pytest.mark.parametrize("n", [3, 16, 20, 24, 36, 100, 128, 252, 256, 260])
+@pytest.mark.parametrize("n", TSP_STEP_N)
 @pytest.mark.parametrize("b", [1, 15, 16, 17, 33, 1000])
 def test_tsp_step_kernel_paths_vs_reference(dev, b, n):
-    """co_tsp_step on arbitrary (not policy-reachable) states through every kernel path
-    (the flat 16-byte-chunk kernel for N % 4 == 0, 16 <= N <= 256 incl. the partial last
-    wave's tail dwords; the lane-group and tile kernels otherwise): random mask bytes with
-    all-zero rows, actions at chunk / row boundaries, out-of-range actions (status bit, no
-    byte cleared), first_mode 0 / 1, in and out of place -- against tsp/env.py:67-93."""
+    """co_tsp_step on arbitrary (not policy-reachable) states through every kernel it
+    launches, at both ends of each one's range (the table in tests/steps_cases.py): the
+    lane-group kernel tsp_step_group_kernel<G> for N % 4 == 0 up to 1024 -- G = 2 (N 4 ..
+    32), 4 (36 .. 64), 8 (68 .. 128), 16 (132 .. 256), 32 (260 .. 512), 64 (516 .. 1024),
+    64 / G rows per wave, incl. the partial last wave -- and the 64-row tile kernel
+    tsp_step_kernel otherwise (N = 3, N = 1028): random mask bytes with all-zero rows,
+    actions at the first and last byte of a row, out-of-range actions (status bit, no byte
+    cleared), first_mode 0 / 1, in and out of place -- against tsp/env.py:67-93."""
     from rl4co_slap_amd import _native as nat
 
     g = torch.Generator().manual_seed(b * 1000 + n)

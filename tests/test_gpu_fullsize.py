@@ -136,17 +136,26 @@ def test_slap_config4_full_batch(dev, b):
         for k in ("actions", "assignment", "action_mask", "i", "done"):
             assert torch.equal(ss[k].cpu(), sc[k].cpu()), k
         _close(ss["reward"].cpu(), sc["reward"].cpu())
+    # the stepwise engine with 10 steps per launch, what the benchmark's chunked mode runs
+    # (bench.SLAP_CHUNK): held to the oracle on the slice below
+    ch = SLAPStepwiseEpisode(td, policy="closest", chunk=10)
+    ch.run_eager()
+    torch.cuda.synchronize()
+    assert int(ch.status.item()) == 0
+    sk = ch.final_state()
+    _slap_props(sk, b)
     # the oracle on a slice of the same batch, both policies
     env = SLAPOracle(seed=1234)
     keys = ("locs", "picklist", "depot_loc_dist", "assignment", "freq")
-    for pol, st_ in (("closest", sc), ("teacher", st)):
+    for pol, sts in (("closest", (sc, sk)), ("teacher", (st,))):
         tds = env.reset(TD({k: gen[k][SLICE].clone() for k in keys}, [512]))
         if pol == "closest":
             r, tdf, a = ref_rollout(env, tds, slap_closest_free_action)
         else:
             it = iter(range(20))
             r, tdf, a = ref_rollout(env, tds, lambda t: acts_t[SLICE][:, next(it)])
-        assert torch.equal(st_["actions"].cpu()[SLICE], a)
-        for k in ("action_mask", "assignment", "i", "done"):
-            assert torch.equal(st_[k].cpu()[SLICE], tdf[k]), (pol, k)
-        _close(st_["reward"].cpu()[SLICE], r)
+        for st_ in sts:
+            assert torch.equal(st_["actions"].cpu()[SLICE], a)
+            for k in ("action_mask", "assignment", "i", "done"):
+                assert torch.equal(st_[k].cpu()[SLICE], tdf[k]), (pol, k)
+            _close(st_["reward"].cpu()[SLICE], r)

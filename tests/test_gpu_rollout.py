@@ -18,7 +18,9 @@ STEPS = functools.partial(TSPFusedEpisode, layout="steps")
 LAYOUTS = pytest.mark.parametrize("fused", [ROWS, STEPS], ids=["rows", "steps"])
 
 
+@functools.lru_cache(maxsize=None)
 def _ref(b, n, seed, policy):
+    """The oracle's rollout, computed once per shape and shared (read only)."""
     env = TSPOracle(num_loc=n, seed=seed)
     td = env.reset(batch_size=[b])
     locs = td["locs"].clone()
@@ -46,6 +48,20 @@ def _check(state, a, r, tdf, exact_reward=False):
 @pytest.mark.parametrize("b,n", [(1, 5), (100, 20), (256, 100), (77, 64), (65, 65), (40, 150)])
 @pytest.mark.parametrize("policy", ["teacher", "nearest"])
 def test_tsp_rollout_matches_oracle(dev, cls, b, n, policy):
+    _tsp_rollout_matches_oracle(dev, cls, b, n, policy)
+
+
+@pytest.mark.parametrize("chunk", [2, 10, 33])
+@pytest.mark.parametrize("b,n", [(1, 5), (100, 20), (256, 100), (77, 64), (65, 65), (40, 150)])
+def test_tsp_rollout_chunked_matches_oracle(dev, b, n, chunk):
+    """The stepwise class with the teacher policy and ``chunk`` env steps per co_tsp_steps
+    launch, against the oracle as above: (40, 150) with chunk 10 runs 15 launches of the
+    G = 16 kernel, (256, 100) the G = 8 kernel, the others its single-step fallback."""
+    cls = functools.partial(TSPStepwiseEpisode, chunk=chunk)
+    _tsp_rollout_matches_oracle(dev, cls, b, n, "teacher")
+
+
+def _tsp_rollout_matches_oracle(dev, cls, b, n, policy):
     locs, a, r, tdf = _ref(b, n, 1234 + n, policy)
     ep = cls(locs.to(dev), a.to(dev) if policy == "teacher" else None, policy=policy)
     ep.run_eager()
@@ -73,6 +89,16 @@ def test_tsp_fused_invalid_tour_flag(dev, fused):
 
 @LAYOUTS
 def test_tsp_fused_full_size_properties(dev, fused):
+    _tsp_full_size_properties(dev, fused)
+
+
+def test_tsp_stepwise_chunked_full_size_properties(dev):
+    """The same spot check on the stepwise episode with 10 env steps per launch, what the
+    benchmark's tsp_stepwise_chunked mode runs."""
+    _tsp_full_size_properties(dev, functools.partial(TSPStepwiseEpisode, chunk=10))
+
+
+def _tsp_full_size_properties(dev, fused):
     # BASELINE config 2 size: size-independent properties (oracle too slow to mirror whole)
     b, n = 65536, 100
     g = torch.Generator().manual_seed(1234)
@@ -154,7 +180,9 @@ def test_tsp_fused_split_tail_tiles_final_state(dev, b, fused):
     assert ((got - ref).abs() <= 1e-5 * ref.abs().clamp(min=1)).all()
 
 
+@functools.lru_cache(maxsize=None)
 def _slap_ref(b, seed, policy):
+    """The oracle's rollout, computed once per batch and policy and shared (read only)."""
     import numpy as np
 
     from oracle.envs import SLAPOracle, slap_closest_free_action
@@ -178,12 +206,24 @@ def _slap_ref(b, seed, policy):
 @pytest.mark.parametrize("b", [1, 64, 100, 300])
 @pytest.mark.parametrize("policy", ["teacher", "closest"])
 def test_slap_rollout_matches_oracle(dev, cls_name, b, policy):
+    _slap_rollout_matches_oracle(dev, cls_name, b, policy)
+
+
+@pytest.mark.parametrize("chunk", [2, 7, 10, 20])
+@pytest.mark.parametrize("b", [1, 64, 100, 300])
+def test_slap_rollout_chunked_matches_oracle(dev, b, chunk):
+    """SLAPStepwiseEpisode with the closest-free policy and ``chunk`` steps per
+    co_slap_closest_steps launch, against the oracle as above."""
+    _slap_rollout_matches_oracle(dev, "SLAPStepwiseEpisode", b, "closest", chunk=chunk)
+
+
+def _slap_rollout_matches_oracle(dev, cls_name, b, policy, **kw):
     import rl4co_slap_amd.rollout.engine as eng
     from rl4co_slap_amd.td import TensorDict
 
     gen, a, r, tdf = _slap_ref(b, 1234 + b, policy)
     td = TensorDict({k: v.clone() for k, v in gen.items()}, [b]).to(dev)
-    ep = getattr(eng, cls_name)(td, a.to(dev) if policy == "teacher" else None, policy=policy)
+    ep = getattr(eng, cls_name)(td, a.to(dev) if policy == "teacher" else None, policy=policy, **kw)
     ep.run_eager()
     torch.cuda.synchronize()
     assert int(ep.status.item()) == 0
@@ -201,6 +241,22 @@ def test_slap_rollout_matches_oracle(dev, cls_name, b, policy):
 @pytest.mark.parametrize("dist", ["grid", "random_ties", "zeros_inf"])
 @pytest.mark.parametrize("cls_name", ["SLAPFusedEpisode", "SLAPStepwiseEpisode"])
 def test_slap_fused_closest_sizes(dev, aisles, locs, prods, orders, dist, cls_name):
+    _slap_closest_sizes(dev, aisles, locs, prods, orders, dist, cls_name)
+
+
+@pytest.mark.parametrize("aisles,locs,prods,orders", [(6, 8, 12, 9), (12, 15, 40, 25),
+                                                      (10, 10, 20, 20), (4, 5, 19, 7),
+                                                      (7, 7, 20, 9)])
+@pytest.mark.parametrize("dist", ["grid", "random_ties", "zeros_inf"])
+@pytest.mark.parametrize("chunk", [2, 7, 10, 20])
+def test_slap_chunked_closest_sizes(dev, aisles, locs, prods, orders, dist, chunk):
+    """The same episodes through SLAPStepwiseEpisode with ``chunk`` steps per
+    co_slap_closest_steps launch: 1 / 2 / 3 units of 4 locations per lane (L = 49 takes the
+    single-step fallback), a lane's sorted keys running dry, ties, -0.0 and +inf."""
+    _slap_closest_sizes(dev, aisles, locs, prods, orders, dist, "SLAPStepwiseEpisode", chunk=chunk)
+
+
+def _slap_closest_sizes(dev, aisles, locs, prods, orders, dist, cls_name, **kw):
     """Closest-free episodes for every lane-group width of the fused kernel (L = 48 -> 8
     lanes, 100 -> 16, 180 -> 32), P close to L - 1 (a lane's sorted list runs dry), and
     depot distances with many exact ties at random positions; the stepwise engine's
@@ -230,7 +286,7 @@ def test_slap_fused_closest_sizes(dev, aisles, locs, prods, orders, dist, cls_na
     td = env.reset(TD({k: v.clone() for k, v in gen.items()}, [b]))
     r, tdf, a = ref_rollout(env, td, slap_closest_free_action)
     ep = getattr(eng, cls_name)(TensorDict({k: v.clone() for k, v in gen.items()}, [b]).to(dev),
-                                None, policy="closest")
+                                None, policy="closest", **kw)
     ep.run_eager()
     torch.cuda.synchronize()
     assert int(ep.status.item()) == 0

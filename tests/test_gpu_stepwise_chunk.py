@@ -47,7 +47,7 @@ def _run(b, n, k, acts, st0, first_mode, chunked, dev):
     return bufs, cur, done, rew, int(status.item())
 
 
-@pytest.mark.parametrize("n", [100, 20, 32, 64, 128, 256, 1000, 7, 3])
+@pytest.mark.parametrize("n", [100, 20, 32, 64, 128, 256, 260, 512, 1000, 7, 3])
 @pytest.mark.parametrize("b,k", [(1, 1), (63, 2), (1000, 7), (4096, 10)])
 @pytest.mark.parametrize("first_mode", [0, 1])
 def test_steps_equal_single_steps(dev, n, b, k, first_mode):
