@@ -825,6 +825,136 @@ int co_episode_stack(int64_t batch, int64_t steps, const int64_t* act_sm, int64_
                      const float* logp_sm, int64_t logp_rs, int64_t* actions, float* logprobs,
                      float* ll, int32_t* status, void* stream);
 
+/* --------------------------------------------------------------- CVRPTW */
+
+/* CVRP with time windows (rl4co/envs/routing/cvrptw/env.py).  N = customers, NC = N + 1
+ * columns (the depot first), 1 <= N <= CO_CVRPTW_MAX_N, else CO_E_INVAL; an empty batch is
+ * a no-op; a NULL pointer not marked nullable is CO_E_INVAL.
+ *
+ * Dtypes.  `durations` [B, NC] and `time_windows` [B, NC, 2] (start, end) arrive in the
+ * td's own dtype with a code CO_DT_* (the generator gives f32 durations and i32 windows,
+ * f32 windows with scale=True; extract_from_solomon gives i64 for both); an unknown code is
+ * CO_E_MODE.  Every value is converted with a plain cast to f32 on load, which is torch's
+ * promotion of an integer tensor meeting the f32 current_time / distances.
+ *
+ * Distance.  dist(p, q) = sqrtf(dx*dx + dy*dy), dx = p.x - q.x, dy = p.y - q.y, in f32,
+ * every operation rounded on its own (no FMA), sqrtf correctly rounded: the value
+ * co_distance_matrix writes.  This is the product's formula and is NOT bit-equal to
+ * torch's CPU norm(p=2) (get_distance, utils/ops.py): over random legs in [0, 150]^2 about
+ * 8 % differ, each by one ulp.
+ *
+ * The mask of a state (get_action_mask, env.py:103-115), c = 0..N:
+ *   current_loc  = locs[b, clamp(current_node, 0, N)]
+ *   distances[c] = dist(current_loc, locs[b, c])
+ *   cvrp[c]      = co_cvrp_action_mask's value: a customer is open when not visited and
+ *                  not (demand[c-1] + used > vehicle_capacity); the depot is open unless
+ *                  (current_node == 0 and some customer is open) -- "open" before the time
+ *                  test, as the reference computes the depot column from the CVRP mask
+ *   action_mask[c] = cvrp[c] && (current_time + distances[c] <= (f32)time_windows[c][1])
+ * The deadline test is f32, applies to the depot column too, and is false for a NaN.
+ *
+ * The step (env.py:117-134), a = action[b], ac = clamp(a, 0, N); a outside 0..N sets
+ * CO_ST_INDEX_RANGE and leaves `visited` unchanged, as co_cvrp_step does:
+ *   x = max(current_time_in + distances_in[b, ac], (f32)time_windows[ac][0])
+ *       (torch.max: NaN when either operand is NaN) + (f32)durations[ac]
+ *   current_time = (float)(a != 0) * x              (so 0 * NaN stays NaN)
+ *   then co_cvrp_step's sequence unchanged (used = (used + d) * (float)(a != 0), visited,
+ *   current_node = a, done = sum(visited) == NC, reward = 0), then the mask above on the
+ *   new state.  distances_in is the vector the previous mask call left in the td. */
+#define CO_CVRPTW_MAX_N 1023
+#define CO_DT_F32 0
+#define CO_DT_I32 1
+#define CO_DT_I64 2
+
+/* status bits of co_cvrptw_check, one per message of check_solution_validity
+ * (cvrptw/env.py:172-218), in the reference's order */
+#define CO_ST_TW_NEGATIVE 64          /* "Time windows must be non-negative."       :182 */
+#define CO_ST_TW_DEPOT_RETURN 128     /* "vehicle cannot perform service and get back to
+                                         depot in time."                            :183-186 */
+#define CO_ST_DURATION_NEGATIVE 256   /* "Service durations must be non-negative."  :187-189 */
+#define CO_ST_TW_INFEASIBLE 512       /* "there are unfeasible time windows"        :190-192 */
+#define CO_ST_TW_DEADLINE 1024        /* "vehicle cannot start service before deadline" :208-213 */
+
+/* CVRPTWEnv._reset (env.py:136-165) in one launch: co_cvrp_reset's outputs plus
+ * current_time[B,1] = 0, current_loc[B,2] = depot, distances[B,NC] and the mask above. */
+int co_cvrptw_reset(int64_t batch, int64_t num_loc, const float* depot, const float* locs_in,
+                    const float* demand, float vehicle_capacity, const void* time_windows,
+                    int tw_dtype, float* locs_out, int64_t* current_node, float* current_time,
+                    float* used_capacity, float* vehicle_capacity_out, uint8_t* visited,
+                    float* current_loc, float* distances, uint8_t* action_mask, void* stream);
+
+/* CVRPTWEnv._step (env.py:117-134) in one launch: the time update, CVRP's step and the new
+ * mask, as stated above.  locs is the post-reset [B, NC, 2].  visited_out may be visited_in
+ * (in-place allowed); every other output is a buffer of its own.  status / not_done
+ * (nullable) as in co_cvrp_step.  One step moves 27 N + 77 bytes per row with i32 / f32
+ * windows (locs 8 NC, windows 8 NC, demand 4 N, visited NC in and NC out, distances 4 NC
+ * and the mask NC out, 54 bytes of row scalars; i64 windows: 8 NC more), about 2.8 KB at
+ * N = 100, against NC square roots: the kernel is bandwidth-bound. */
+int co_cvrptw_step(int64_t batch, int64_t num_loc, const int64_t* action, const float* locs,
+                   const float* demand, const float* used_in, float* used_out,
+                   const float* vehicle_capacity, const uint8_t* visited_in,
+                   uint8_t* visited_out, const float* current_time_in,
+                   const float* distances_in, const void* durations, int dur_dtype,
+                   const void* time_windows, int tw_dtype, float* current_time_out,
+                   int64_t* current_out, uint8_t* done, uint8_t* reward, float* current_loc,
+                   float* distances, uint8_t* action_mask, int32_t* status, int32_t* not_done,
+                   void* stream);
+
+/* CVRPTWEnv.get_action_mask alone (env.py:103-115); also writes current_loc [B,2] and
+ * distances [B,NC], which the reference stores in the td.  current_node / current_time are
+ * [B,1]. */
+int co_cvrptw_action_mask(int64_t batch, int64_t num_loc, const float* locs, const float* demand,
+                          const float* used, const float* vehicle_capacity,
+                          const uint8_t* visited, const int64_t* current_node,
+                          const float* current_time, const void* time_windows, int tw_dtype,
+                          float* current_loc, float* distances, uint8_t* action_mask,
+                          void* stream);
+
+/* The time-window part of check_solution_validity (env.py:176-218; CVRP's part is
+ * co_cvrp_reward with check != 0) for actions [B, T] (element (b, t) at b*act_stride_b +
+ * t*act_stride_t).  With tw = (f32)time_windows, dur = (f32)durations, d0[c] = dist(locs[b,
+ * 0], locs[b, c]), per row and column:
+ *   tw < 0 (either end)                                       CO_ST_TW_NEGATIVE
+ *   !((tw[c][0] + d0[c]) + dur[c] <= tw[0][0][1])             CO_ST_TW_DEPOT_RETURN
+ *       -- the bound is the depot deadline OF BATCH ROW 0, as in the reference, read on
+ *       the device (no host sync)
+ *   dur[c] < 0                                                CO_ST_DURATION_NEGATIVE
+ *   !(tw[c][0] < tw[c][1])                                    CO_ST_TW_INFEASIBLE
+ * then the scan from t = 0 at the depot, per action a (out of 0..N: CO_ST_INDEX_RANGE, the
+ * row's scan ends):
+ *   t = max(trunc(t + dist(locs[prev], locs[a])), tw[a][0]); !(t <= tw[a][1]) sets
+ *   CO_ST_TW_DEADLINE; t += dur[a]; t = 0 when a == 0.
+ * trunc is the reference's `.int()`: toward zero, and -2^31 for a NaN or a value outside
+ * int32 (what the x86 conversion gives).  All of it in f32 (integer windows below 2^24 are
+ * exact).  The reference's "Distances must be non-negative." (:181) cannot fail for finite
+ * coordinates -- a square root is never negative -- and has no bit. */
+int co_cvrptw_check(int64_t batch, int64_t num_loc, int64_t steps, const float* locs,
+                    const int64_t* actions, int64_t act_stride_b, int64_t act_stride_t,
+                    const void* durations, int dur_dtype, const void* time_windows,
+                    int tw_dtype, int32_t* status, void* stream);
+
+/* `steps` (>= 1) preset co_cvrptw_step calls in one launch: action (t, b) at
+ * actions[t*act_stride_t + b*act_stride_b].  used / visited / current_time / current_node
+ * are updated in place ([B,1] / [B,NC]); distances_in [B,NC] is the vector of the state's
+ * mask call (step 0's leg is distances_in[b, a_0], as in co_cvrptw_step); done, reward,
+ * current_loc, distances and action_mask are written for the last step.  The final state is
+ * that of the `steps` single calls bit for bit: a later step's leg distances[a] is
+ * dist(locs[current_node], locs[a]), the same expression the single step's mask call
+ * stored.  feasible (nullable, u8 [steps, B]): the value action_mask[b, a_t] had before
+ * step t (0 for an a_t outside 0..N); time (nullable, f32 [steps, B]): current_time after
+ * step t.  not_done counts the rows not done after the last step.  On the device a row's
+ * coordinates, windows, durations, demands and visited set stay in registers for the whole
+ * call; per step the action is read and feasible / time written. */
+int co_cvrptw_steps(int64_t batch, int64_t num_loc, int64_t steps, const int64_t* actions,
+                    int64_t act_stride_t, int64_t act_stride_b, const float* locs,
+                    const float* demand, float* used, const float* vehicle_capacity,
+                    uint8_t* visited, float* current_time, int64_t* current_node,
+                    const float* distances_in, const void* durations, int dur_dtype,
+                    const void* time_windows, int tw_dtype, uint8_t* done, uint8_t* reward,
+                    float* current_loc, float* distances, uint8_t* action_mask,
+                    uint8_t* feasible, float* time, int32_t* status, int32_t* not_done,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

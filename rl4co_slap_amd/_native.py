@@ -96,6 +96,12 @@ _SIGS = {
     "co_symmetric_augment": [_i64, _i64, _p, _p, _f32, _p, _p],
     "co_cvrp_rollout": [_i64, _i64, _p, _p, _p, _f32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                         _p, _p, _p, _p, _p],
+    "co_cvrptw_reset": [_i64, _i64, _p, _p, _p, _f32, _p, _i32] + [_p] * 10,
+    "co_cvrptw_step": [_i64, _i64] + [_p] * 11 + [_i32, _p, _i32] + [_p] * 10,
+    "co_cvrptw_action_mask": [_i64, _i64] + [_p] * 8 + [_i32, _p, _p, _p, _p],
+    "co_cvrptw_check": [_i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i32, _p, _i32, _p, _p],
+    "co_cvrptw_steps": [_i64, _i64, _i64, _p, _i64, _i64] + [_p] * 9 + [_i32, _p, _i32]
+                       + [_p] * 10,
 }
 
 ST_INVALID_TOUR = 1
@@ -104,6 +110,11 @@ ST_INFEASIBLE = 4
 ST_INDEX_RANGE = 8
 ST_TRUNCATED = 16
 ST_LOGP_NEG_INF = 32
+# CO_ST_TW_*: co_cvrptw_check's bits, one per message of the reference's check
+ST_TW_NEGATIVE, ST_TW_DEPOT_RETURN, ST_DURATION_NEGATIVE = 64, 128, 256
+ST_TW_INFEASIBLE, ST_TW_DEADLINE = 512, 1024
+CVRPTW_MAX_N = 1023  # CO_CVRPTW_MAX_N: the most customers the CVRPTW entries take
+DT_F32, DT_I32, DT_I64 = 0, 1, 2  # CO_DT_*: dtype codes of durations / time_windows
 DECODE_FAST = 0x100  # CO_DECODE_FAST mode flag (opt-in fast math; not bit-exact)
 DECODE_CERTIFIED = 0x200  # CO_DECODE_CERTIFIED: fast math, greedy actions certified exact
 TWO_OPT_MAX_N = 1024  # CO_TWO_OPT_MAX_N: the longest tour co_tsp_two_opt takes
@@ -180,6 +191,8 @@ HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt"
                 "co_tsp_kopt_step", "co_tsp_kopt_steps", "co_tsp_nearest_rec",
                 "co_cvrp_reset", "co_cvrp_step", "co_cvrp_action_mask", "co_cvrp_reward",
                 "co_cvrp_local_search",
+                "co_cvrptw_reset", "co_cvrptw_step", "co_cvrptw_action_mask", "co_cvrptw_check",
+                "co_cvrptw_steps",
                 "co_slap_reset", "co_slap_step", "co_slap_reward", "co_slap_local_search",
                 "co_gather_by_index", "co_best_of", "co_tsp_best_of",
                 "co_decode_step"]

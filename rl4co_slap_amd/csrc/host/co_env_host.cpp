@@ -1314,6 +1314,258 @@ CO_HOST_API int co_tsp_nearest_rec(int64_t B, int64_t N, const float* locs, int6
   return CO_OK;
 }
 
+// -------------------------------------------------------------------------- CVRPTW
+// cvrptw/env.py in its plain scalar form; co_env.h states the semantics.  co_cvrptw_steps
+// is literally `steps` single steps per row, each with its full distance vector.
+namespace {
+inline float tw_ldf(const void* p, int dt, int64_t i) {
+  if (dt == CO_DT_F32) return static_cast<const float*>(p)[i];
+  if (dt == CO_DT_I32) return (float)static_cast<const int32_t*>(p)[i];
+  return (float)static_cast<const int64_t*>(p)[i];
+}
+inline float tw_dist(float px, float py, float qx, float qy) {
+  const float dx = px - qx, dy = py - qy;
+  return std::sqrt(dx * dx + dy * dy);
+}
+inline float tw_max(float p, float s) {
+  return (p != p || s != s) ? __builtin_nanf("") : (p > s ? p : s);
+}
+inline float tw_trunc(float x) {
+  return (x >= -2147483648.f && x < 2147483648.f) ? (float)(int32_t)x : -2147483648.f;
+}
+inline bool tw_dt_ok(int dt) { return dt == CO_DT_F32 || dt == CO_DT_I32 || dt == CO_DT_I64; }
+inline bool tw_sizes_ok(int64_t B, int64_t N) { return B >= 0 && N > 0 && N <= CO_CVRPTW_MAX_N; }
+inline bool tw_mis8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) != 0; }
+
+// get_action_mask (cvrptw/env.py:103-115) of one row; lr = the row's [NC, 2] coordinates,
+// twr = the row's first window element index
+void tw_mask_row(int64_t N, const float* lr, const float* dem, float used, float cap,
+                 const uint8_t* vis, int64_t cur, float tnow, const void* tw, int tw_dt,
+                 int64_t twr, float* cur_loc, float* dist, uint8_t* mask) {
+  const int64_t cc = cur < 0 ? 0 : (cur > N ? N : cur);
+  const float cx = lr[2 * cc], cy = lr[2 * cc + 1];
+  cur_loc[0] = cx;
+  cur_loc[1] = cy;
+  cvrp_mask_row(N, dem, used, cap, vis, cur, mask);
+  for (int64_t c = 0; c <= N; ++c) {
+    const float d = tw_dist(cx, cy, lr[2 * c], lr[2 * c + 1]);
+    dist[c] = d;
+    mask[c] = mask[c] && (tnow + d <= tw_ldf(tw, tw_dt, twr + 2 * c + 1));
+  }
+}
+
+// one step of one row on its state (cvrptw/env.py:117-134, cvrp/env.py:73-105); returns
+// whether the action was in range.  dleg = distances_in[clamp(a)]
+bool tw_step_row(int64_t N, int64_t a, const float* dem, float& used, uint8_t* vis, float& tnow,
+                 float dleg, const void* dur, int dur_dt, int64_t durr, const void* tw,
+                 int tw_dt, int64_t twr) {
+  const bool bad = a < 0 || a > N;
+  const int64_t ac = a < 0 ? 0 : (a > N ? N : a);
+  int64_t di = a - 1;
+  di = di < 0 ? 0 : (di > N - 1 ? N - 1 : di);
+  const float m01 = a != 0 ? 1.0f : 0.0f;
+  tnow = m01 * (tw_max(tnow + dleg, tw_ldf(tw, tw_dt, twr + 2 * ac)) +
+                tw_ldf(dur, dur_dt, durr + ac));
+  used = (used + dem[di]) * m01;
+  if (!bad) vis[a] = 1;
+  return !bad;
+}
+}  // namespace
+
+CO_HOST_API int co_cvrptw_reset(int64_t B, int64_t N, const float* depot, const float* locs_in,
+                                const float* demand, float vcap, const void* tw, int tw_dt,
+                                float* locs_out, int64_t* cur, float* time, float* used,
+                                float* vcap_out, uint8_t* visited, float* cur_loc, float* dist,
+                                uint8_t* mask, void*) {
+  if (!tw_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!depot || !locs_in || !demand || !tw || !locs_out || !cur || !time || !used || !vcap_out ||
+      !visited || !cur_loc || !dist || !mask)
+    return CO_E_INVAL;
+  if (!tw_dt_ok(tw_dt)) return CO_E_MODE;
+  if (tw_mis8(depot) || tw_mis8(locs_in) || tw_mis8(locs_out) || tw_mis8(cur_loc))
+    return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b) {
+    float* lo = locs_out + b * NC * 2;
+    lo[0] = depot[2 * b];
+    lo[1] = depot[2 * b + 1];
+    std::memcpy(lo + 2, locs_in + b * N * 2, sizeof(float) * 2 * (size_t)N);
+    std::memset(visited + b * NC, 0, (size_t)NC);
+    cur[b] = 0;
+    time[b] = 0.f;
+    used[b] = 0.f;
+    vcap_out[b] = vcap;
+    tw_mask_row(N, lo, demand + b * N, 0.f, vcap, visited + b * NC, 0, 0.f, tw, tw_dt,
+                2 * b * NC, cur_loc + 2 * b, dist + b * NC, mask + b * NC);
+  }
+  return CO_OK;
+}
+
+CO_HOST_API int co_cvrptw_step(int64_t B, int64_t N, const int64_t* action, const float* locs,
+                               const float* demand, const float* used_in, float* used_out,
+                               const float* vcap, const uint8_t* vis_in, uint8_t* vis_out,
+                               const float* t_in, const float* dist_in, const void* dur,
+                               int dur_dt, const void* tw, int tw_dt, float* t_out,
+                               int64_t* cur_out, uint8_t* done, uint8_t* reward, float* cur_loc,
+                               float* dist, uint8_t* mask, int32_t* status, int32_t* not_done,
+                               void*) {
+  if (!tw_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!action || !locs || !demand || !used_in || !used_out || !vcap || !vis_in || !vis_out ||
+      !t_in || !dist_in || !dur || !tw || !t_out || !cur_out || !done || !reward || !cur_loc ||
+      !dist || !mask)
+    return CO_E_INVAL;
+  if (!tw_dt_ok(tw_dt) || !tw_dt_ok(dur_dt)) return CO_E_MODE;
+  if (tw_mis8(locs) || tw_mis8(cur_loc)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  int32_t left = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t a = action[b];
+    const int64_t ac = a < 0 ? 0 : (a > N ? N : a);
+    uint8_t* vo = vis_out + b * NC;
+    if (vo != vis_in + b * NC) std::memcpy(vo, vis_in + b * NC, (size_t)NC);
+    float used = used_in[b], tnow = t_in[b];
+    if (!tw_step_row(N, a, demand + b * N, used, vo, tnow, dist_in[b * NC + ac], dur, dur_dt,
+                     b * NC, tw, tw_dt, 2 * b * NC))
+      set_status(status, CO_ST_INDEX_RANGE);
+    int64_t vsum = 0;
+    for (int64_t c = 0; c < NC; ++c) vsum += vo[c];
+    used_out[b] = used;
+    t_out[b] = tnow;
+    cur_out[b] = a;
+    done[b] = vsum == NC;
+    left += vsum != NC;
+    reward[b] = 0;
+    tw_mask_row(N, locs + b * NC * 2, demand + b * N, used, vcap[b], vo, a, tnow, tw, tw_dt,
+                2 * b * NC, cur_loc + 2 * b, dist + b * NC, mask + b * NC);
+  }
+  if (not_done) *not_done += left;
+  return CO_OK;
+}
+
+CO_HOST_API int co_cvrptw_action_mask(int64_t B, int64_t N, const float* locs,
+                                      const float* demand, const float* used, const float* vcap,
+                                      const uint8_t* visited, const int64_t* cur,
+                                      const float* time, const void* tw, int tw_dt,
+                                      float* cur_loc, float* dist, uint8_t* mask, void*) {
+  if (!tw_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!locs || !demand || !used || !vcap || !visited || !cur || !time || !tw || !cur_loc ||
+      !dist || !mask)
+    return CO_E_INVAL;
+  if (!tw_dt_ok(tw_dt)) return CO_E_MODE;
+  if (tw_mis8(locs) || tw_mis8(cur_loc)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b)
+    tw_mask_row(N, locs + b * NC * 2, demand + b * N, used[b], vcap[b], visited + b * NC, cur[b],
+                time[b], tw, tw_dt, 2 * b * NC, cur_loc + 2 * b, dist + b * NC, mask + b * NC);
+  return CO_OK;
+}
+
+CO_HOST_API int co_cvrptw_check(int64_t B, int64_t N, int64_t T, const float* locs,
+                                const int64_t* actions, int64_t sb, int64_t st, const void* dur,
+                                int dur_dt, const void* tw, int tw_dt, int32_t* status, void*) {
+  if (!tw_sizes_ok(B, N) || T < 0 || T > (1 << 20)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!locs || (T > 0 && !actions) || !dur || !tw || !status) return CO_E_INVAL;
+  if (!tw_dt_ok(tw_dt) || !tw_dt_ok(dur_dt)) return CO_E_MODE;
+  const int64_t NC = N + 1;
+  const float deadline0 = tw_ldf(tw, tw_dt, 1);  // time_windows[0, 0, 1]
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t row = b * NC;
+    const float* lr = locs + 2 * row;
+    int32_t bits = 0;
+    for (int64_t c = 0; c < NC; ++c) {
+      const float s = tw_ldf(tw, tw_dt, 2 * (row + c)), e = tw_ldf(tw, tw_dt, 2 * (row + c) + 1);
+      const float du = tw_ldf(dur, dur_dt, row + c);
+      const float d0 = tw_dist(lr[0], lr[1], lr[2 * c], lr[2 * c + 1]);
+      if (s < 0.f || e < 0.f) bits |= CO_ST_TW_NEGATIVE;
+      if (!((s + d0) + du <= deadline0)) bits |= CO_ST_TW_DEPOT_RETURN;
+      if (du < 0.f) bits |= CO_ST_DURATION_NEGATIVE;
+      if (!(s < e)) bits |= CO_ST_TW_INFEASIBLE;
+    }
+    float t = 0.f;
+    int64_t prev = 0;
+    for (int64_t k = 0; k < T; ++k) {
+      const int64_t a = actions[b * sb + k * st];
+      if (a < 0 || a > N) {
+        bits |= CO_ST_INDEX_RANGE;
+        break;
+      }
+      const float d = tw_dist(lr[2 * prev], lr[2 * prev + 1], lr[2 * a], lr[2 * a + 1]);
+      t = tw_max(tw_trunc(t + d), tw_ldf(tw, tw_dt, 2 * (row + a)));
+      if (!(t <= tw_ldf(tw, tw_dt, 2 * (row + a) + 1))) bits |= CO_ST_TW_DEADLINE;
+      t = t + tw_ldf(dur, dur_dt, row + a);
+      if (a == 0) t = 0.f;
+      prev = a;
+    }
+    if (bits) set_status(status, bits);
+  }
+  return CO_OK;
+}
+
+CO_HOST_API int co_cvrptw_steps(int64_t B, int64_t N, int64_t T, const int64_t* actions,
+                                int64_t st, int64_t sb, const float* locs, const float* demand,
+                                float* used, const float* vcap, uint8_t* visited, float* time_io,
+                                int64_t* cur, const float* dist_in, const void* dur, int dur_dt,
+                                const void* tw, int tw_dt, uint8_t* done, uint8_t* reward,
+                                float* cur_loc, float* dist, uint8_t* mask, uint8_t* feasible,
+                                float* time, int32_t* status, int32_t* not_done, void*) {
+  if (!tw_sizes_ok(B, N) || T < 1 || T > (1 << 20)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!actions || !locs || !demand || !used || !vcap || !visited || !time_io || !cur ||
+      !dist_in || !dur || !tw || !done || !reward || !cur_loc || !dist || !mask)
+    return CO_E_INVAL;
+  if (!tw_dt_ok(tw_dt) || !tw_dt_ok(dur_dt)) return CO_E_MODE;
+  if (tw_mis8(locs) || tw_mis8(cur_loc)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  std::vector<float> dv((size_t)NC);
+  std::vector<uint8_t> mv((size_t)NC);
+  int32_t left = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const float* lr = locs + b * NC * 2;
+    const float* dem = demand + b * N;
+    uint8_t* vis = visited + b * NC;
+    float u = used[b], tnow = time_io[b], cl[2];
+    int64_t c_now = cur[b];
+    std::copy(dist_in + b * NC, dist_in + (b + 1) * NC, dv.begin());
+    if (feasible) {  // the mask of the input state on the caller's distances
+      cvrp_mask_row(N, dem, u, vcap[b], vis, c_now, mv.data());
+      for (int64_t c = 0; c < NC; ++c)
+        mv[(size_t)c] = mv[(size_t)c] &&
+                        (tnow + dv[(size_t)c] <= tw_ldf(tw, tw_dt, 2 * (b * NC + c) + 1));
+    }
+    for (int64_t t = 0; t < T; ++t) {
+      const int64_t a = actions[t * st + b * sb];
+      const int64_t ac = a < 0 ? 0 : (a > N ? N : a);
+      const bool bad = a < 0 || a > N;
+      if (feasible) feasible[t * B + b] = !bad && mv[(size_t)ac];
+      if (!tw_step_row(N, a, dem, u, vis, tnow, dv[(size_t)ac], dur, dur_dt, b * NC, tw, tw_dt,
+                       2 * b * NC))
+        set_status(status, CO_ST_INDEX_RANGE);
+      c_now = a;
+      if (time) time[t * B + b] = tnow;
+      tw_mask_row(N, lr, dem, u, vcap[b], vis, a, tnow, tw, tw_dt, 2 * b * NC, cl, dv.data(),
+                  mv.data());
+    }
+    int64_t vsum = 0;
+    for (int64_t c = 0; c < NC; ++c) vsum += vis[c];
+    used[b] = u;
+    time_io[b] = tnow;
+    cur[b] = c_now;
+    done[b] = vsum == NC;
+    left += vsum != NC;
+    reward[b] = 0;
+    cur_loc[2 * b] = cl[0];
+    cur_loc[2 * b + 1] = cl[1];
+    std::copy(dv.begin(), dv.end(), dist + b * NC);
+    std::copy(mv.begin(), mv.end(), mask + b * NC);
+  }
+  if (not_done) *not_done += left;
+  return CO_OK;
+}
+
 CO_HOST_API const char* co_build_info(void) {
   return "rl4co_slap_amd co_env: host (CPU) build of the env / decode entry points";
 }

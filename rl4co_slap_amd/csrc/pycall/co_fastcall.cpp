@@ -6,7 +6,7 @@
 // 'f' float, 'd' double.  On x86-64 System V, integer-class arguments take the general
 // registers and then the stack in their own order and float-class arguments the SSE
 // registers in theirs, independently of how the two classes interleave; so one
-// trampoline typed (24 x int64, 8 x double) reaches every entry point of include/co_env.h:
+// trampoline typed (28 x int64, 8 x double) reaches every entry point of include/co_env.h:
 // surplus integer slots and registers are ignored by the callee, a `float` parameter reads
 // the low 32 bits of its SSE register (the float's bits are placed there), an int32 one the
 // low 32 bits of its register / stack slot.  No torch types, no Python objects cross.
@@ -22,10 +22,11 @@
 
 namespace {
 
-constexpr int kMaxInt = 24, kMaxFp = 8;
+constexpr int kMaxInt = 28, kMaxFp = 8;
 typedef int (*Tramp)(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                      int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                      int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                     int64_t, int64_t, int64_t, int64_t,
                      double, double, double, double, double, double, double, double);
 
 PyObject* invoke(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
@@ -80,7 +81,8 @@ PyObject* invoke(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
     Py_BEGIN_ALLOW_THREADS
     rc = fn(iv[0], iv[1], iv[2], iv[3], iv[4], iv[5], iv[6], iv[7], iv[8], iv[9], iv[10], iv[11],
             iv[12], iv[13], iv[14], iv[15], iv[16], iv[17], iv[18], iv[19], iv[20], iv[21],
-            iv[22], iv[23], fv[0], fv[1], fv[2], fv[3], fv[4], fv[5], fv[6], fv[7]);
+            iv[22], iv[23], iv[24], iv[25], iv[26], iv[27], fv[0], fv[1], fv[2], fv[3], fv[4], fv[5],
+            fv[6], fv[7]);
     Py_END_ALLOW_THREADS
     return PyLong_FromLong(rc);
   }
