@@ -1,7 +1,7 @@
 """Shared inputs and checks of tests/test_host_cvrptw.py (host build) and
 tests/test_gpu_cvrptw.py (device): the recording tests/golden/cvrptw/ref_cvrptw.npz, seeded
-instances with a random-feasible rollout of the restatement (tests/cvrptw_ref.py; computed
-once per shape and shared), thin wrappers over the C ABI entries, and the comparisons.  A
+instances with a random-feasible and a directed rollout of the restatement
+(tests/cvrptw_ref.py; computed once per shape and shared), thin wrappers over the C ABI entries, and the comparisons.  A
 check takes the device it runs on: CPU tensors go to the host build, CUDA tensors to the
 kernels, through the same ``_native.call``."""
 import functools
@@ -138,18 +138,34 @@ def ref_reset(inst):
                      inst["time_windows"])
 
 
+def group_lanes(n):
+    """The lanes that own a row of N customers (csrc/cvrptw.hip, tw_launch): lane sl holds
+    the columns sl + G j, so column c sits in register slot c // G."""
+    nc = n + 1
+    return 8 if nc <= 16 else 16 if nc <= 32 else 32 if nc <= 64 else 64
+
+
 @functools.lru_cache(maxsize=None)
-def rollout(n, b, tw_dtype=torch.int32, max_steps=None):
+def rollout(n, b, tw_dtype=torch.int32, max_steps=None, directed=False):
     """The restatement's random-feasible episode: (states after reset and every step,
-    actions [T, B]).  A row without a feasible action takes the depot."""
+    actions [T, B]).  A row without a feasible action takes the depot.  ``directed``: among
+    the feasible columns a row prefers one whose register slot has not been its action yet,
+    and every second row prefers column N, the last live one, above all."""
     st = ref_reset(instance(n, b, tw_dtype))
     g = np.random.default_rng(n * 7 + b)
     states, actions = [st], []
+    slot = np.arange(n + 1) // group_lanes(n)
+    unseen = np.ones((b, int(slot[-1]) + 1), bool)
+    last = (np.arange(n + 1) == n)[None, :] & (np.arange(b) % 2 == 0)[:, None]
     while not st.get("done", np.zeros(1, bool)).all() and (max_steps is None
                                                            or len(actions) < max_steps):
         m = st["action_mask"]
-        score = np.where(m, g.random(m.shape), -1.0)
+        score = g.random(m.shape)
+        if directed:
+            score = score + 2.0 * unseen[:, slot] + 4.0 * last
+        score = np.where(m, score, -1.0)
         a = np.where(m.any(1), score.argmax(1), 0).astype(np.int64)
+        unseen[np.arange(b), slot[a]] = False
         st, bits = ref.step(st, a)
         assert bits == 0
         states.append(st)
@@ -158,6 +174,23 @@ def rollout(n, b, tw_dtype=torch.int32, max_steps=None):
 
 
 LARGE_SHAPES = [(300, 3), (1023, 2)]  # 8 and 16 columns per lane
+# N + 1 on both sides of every switch of tw_launch: the lanes per row G (8 / 16 / 32 / 64 at
+# 16, 32, 64) and the columns per lane U (2 / 4 / 8 / 16 at 128, 256, 512); B = 3
+SWITCH_SIZES = (15, 16, 31, 32, 62, 127, 128, 255, 256, 511, 512)
+# (N, B) of the directed rollouts: 3, 5, 5, 9 and 16 live register slots
+DIRECTED_SHAPES = [(128, 4), (256, 4), (300, 4), (512, 4), (1023, 4)]
+
+
+def check_directed_inputs(n, b, tw_dtype=torch.int32):
+    """The condition on the inputs of a directed case, from the restatement's rollout alone:
+    every register slot 0 .. ceil((N + 1) / G) - 1 is the action's at least once in the
+    batch, and column N is visited in at least one row."""
+    states, actions = rollout(n, b, tw_dtype, episode_len(n, b), True)
+    g = group_lanes(n)
+    slots = set((actions // g).ravel().tolist())
+    want = set(range(-(-(n + 1) // g)))
+    assert slots == want, f"n{n} b{b}: slots {sorted(want - slots)} are never the action"
+    assert (actions == n).any() and states[-1]["visited"][:, n].any(), f"n{n} b{b}: column N"
 
 
 def episode_len(n, b):
@@ -275,6 +308,52 @@ def abi_check(locs, actions, durations, time_windows):
     return int(status.item())
 
 
+def check_check_bits_two_blocks(device):
+    """co_cvrptw_check on B = 300 (a second 256-thread block with a partial tail), actions
+    step-major and row-major: each status bit provoked alone in row 280, against the
+    restatement's ``check``; and the depot-return bound is batch row 0's for every row."""
+    n, b, r = 20, 300, 280
+    inst = instance(n, b)
+    states, actions = rollout(n, b, max_steps=12)  # [T, B]; a feasible prefix
+    locs_np, dur_np, tw_np = states[0]["locs"], inst["durations"], inst["time_windows"]
+    mine = actions[:, r]
+    free = next(c for c in range(1, n + 1) if c not in mine)  # a column row 280 never visits
+    first = int(mine[0])
+    assert first != 0 and ref.dist(locs_np[r, 0], locs_np[r, first]) >= 2
+    locs = torch.from_numpy(locs_np).to(device)
+
+    def both(want, dur_=dur_np, tw_=tw_np, acts_=actions, what=""):
+        expect = ref.check(locs_np, acts_.T, dur_, tw_)
+        assert expect == want, (what, expect)
+        dur, tw = torch.from_numpy(dur_).to(device), torch.from_numpy(tw_).to(device)
+        a = torch.from_numpy(acts_).to(device)
+        for layout, view in (("step-major", a.t()), ("row-major", a.t().contiguous())):
+            assert view.shape == (b, len(acts_))
+            got = abi_check(locs, view, dur, tw)
+            assert got == expect, (what, layout, got, expect)
+
+    def edited(arr, index, value):
+        out = arr.copy()
+        out[index] = value
+        return out
+
+    both(0, what="untouched")
+    both(nat.ST_TW_NEGATIVE, tw_=edited(tw_np, (r, free, 0), -1), what="negative window")
+    late = edited(edited(tw_np, (r, free, 0), 479), (r, free, 1), 480)
+    both(nat.ST_TW_DEPOT_RETURN, tw_=late, what="no return to the depot in time")
+    both(nat.ST_DURATION_NEGATIVE, dur_=edited(dur_np, (r, free), -1), what="negative duration")
+    both(nat.ST_TW_INFEASIBLE, tw_=edited(tw_np, (r, free, 1), tw_np[r, free, 0]),
+         what="empty window")
+    missed = edited(edited(tw_np, (r, first, 0), 0), (r, first, 1), 1)
+    both(nat.ST_TW_DEADLINE, tw_=missed, what="missed deadline")
+    both(nat.ST_INDEX_RANGE, acts_=edited(actions, (3, r), n + 1), what="action out of range")
+    # deadline0 is time_windows[0, 0, 1] for every row: raising it clears row 280's verdict,
+    # raising row 280's own depot deadline changes nothing
+    both(0, tw_=edited(late, (0, 0, 1), 1000), what="row 0's depot deadline raised")
+    both(nat.ST_TW_DEPOT_RETURN, tw_=edited(late, (r, 0, 1), 1000),
+         what="row 280's depot deadline raised")
+
+
 # ------------------------------------------------------------------ comparisons
 def same_bits(got, want, what):
     """Bit for bit; a NaN matches any NaN (the payload is not part of the contract)."""
@@ -305,12 +384,13 @@ def check_states_equal(a, b, what, keys=STATE + ("done", "reward")):
         same_bits(a[key], b[key].detach().cpu().numpy(), f"{what} {key}")
 
 
-def check_shape(n, b, tw_dtype, device):
+def check_shape(n, b, tw_dtype, device, directed=False):
     """Reset, mask, every single step and co_cvrptw_steps (T = 1, 7, the episode; both
-    action layouts) against the restatement's rollout, bit for bit."""
+    action layouts) against the restatement's rollout (random-feasible or ``directed``), bit
+    for bit."""
     inst = instance(n, b, tw_dtype)
-    states, actions = rollout(n, b, tw_dtype, episode_len(n, b))
-    what = f"n{n} b{b} {tw_dtype}"
+    states, actions = rollout(n, b, tw_dtype, episode_len(n, b), directed)
+    what = f"n{n} b{b} {tw_dtype}" + (" directed" if directed else "")
     st = abi_reset(inst, device)
     same_bits(st["locs"], states[0]["locs"], what + " reset locs")
     check_state(st, states[0], what + " reset")

@@ -1,6 +1,8 @@
 """Shared inputs and checks of tests/test_host_kopt.py and tests/test_gpu_kopt.py: the
-recording tests/golden/kopt/ref_kopt.npz, seeded instances, valid k-opt actions and the
-comparison of a product state with a restatement (tests/kopt_ref.py) state."""
+recording tests/golden/kopt/ref_kopt.npz, seeded instances, valid k-opt actions, the cases
+for k_max = 5, 8, 15, 16 (HIGH_K) and every 2-opt pair of one tour (PAIR_SIZES) with the
+restatement's results, and the comparison of a product state with a restatement
+(tests/kopt_ref.py) state."""
 import functools
 import os
 
@@ -114,6 +116,47 @@ def kopt_actions(g, rec, k, t):
         rec = torch.where(ok[:, None], new, rec)
         out.append(act)
     return torch.stack(out) if out else torch.zeros(0, b, 3 * k, dtype=torch.int64)
+
+
+HIGH_K = [(k, n) for k in (5, 8, 15, 16) for n in (20, 65, 130)]  # up to CO_KOPT_MAX_K
+
+
+@functools.lru_cache(maxsize=None)
+def high_k_case(k, n, b=8, t=3):
+    """(locs, rec, acts [T, B, 3k], the restatement's state after every step) of a seeded
+    case for 5 <= k_max <= 16, computed once and shared: do not write to it.  The conditions
+    on the inputs hold for the restatement alone: every row's tour changes, and every
+    row-step is clear by the recorder's rule (a no-op, or the new cost at least MARGIN
+    relative off the best-so-far cost), so no improvement test hangs on the summation order;
+    a seed that misses either is passed over."""
+    for seed in range(2000 * k + n, 2000 * k + n + 1000, 100):
+        locs, rec, g = instance(b, n, seed)
+        acts = kopt_actions(g, rec, k, t)
+        state, after, clear = kopt_ref.reset(locs, rec.clone()), [], True
+        for a in acts:
+            bsf, before = state["cost_bsf"], state["rec_current"]
+            state = kopt_ref.step(state, a, k)
+            same = (state["rec_current"] == before).all(1)
+            margin = (state["cost_current"] - bsf).abs() / bsf
+            clear &= bool((same | (margin >= MARGIN)).all())
+            after.append({key: v.clone() for key, v in state.items()})
+        if clear and bool((state["rec_current"] != rec).any(1).all()):
+            return locs, rec, acts, after
+    raise AssertionError(f"k{k} n{n}: no seed moves every row with every row-step clear")
+
+
+PAIR_SIZES = [3, 4, 5, 6, 65, 129]  # one lane does all the work; two and three trips of 64
+
+
+@functools.lru_cache(maxsize=None)
+def all_pairs(n):
+    """Every (first, second) of one seeded tour as a batch of B = N * N rows: (pairs, locs,
+    rec, the restatement's step), computed once and shared: do not write to it."""
+    pairs = torch.tensor([(f, s) for f in range(n) for s in range(n)])
+    b = pairs.shape[0]
+    locs, rec, _ = instance(1, n, 40 + n)
+    locs, rec = locs.expand(b, n, 2).contiguous(), rec.expand(b, n).contiguous()
+    return pairs, locs, rec, kopt_ref.step(kopt_ref.reset(locs, rec.clone()), pairs, 2)
 
 
 def two_opt_actions(g, rec, t, special=True):

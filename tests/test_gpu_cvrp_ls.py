@@ -4,7 +4,8 @@ for every size: m = 2..4 (N = 1..3) has empty or one-window strips, N = 50 at ca
 puts m around 60..70 on both sides of one 64-lane window, N = 56 / 57 and 100 give several
 positions per lane in the load scan, N = 400 a long tour.  The distances path stages the
 matrix in LDS up to N = CO_CVRP_LS_STAGE_N and reads it through L2 above, so both sides of
-that cut are run."""
+that cut are run.  The per-instance capacity argument is run at capacity 8 with B = 64, N =
+20 and with 5 instances shared by 15 rows."""
 import numpy as np
 import pytest
 import torch
@@ -113,6 +114,22 @@ def test_multistart_locs_batch_abi_and_env(dev):
     out, sw = env.improve(tdm, torch.as_tensor(tours.copy()).to(dev), return_sweeps=True)
     assert tdm.is_lazy("locs") and tdm.is_lazy("demand")
     _eq((out.cpu().numpy(), sw.cpu().numpy()), (ref, sweeps))
+
+
+def test_capacity_argument(dev):
+    """The per-instance capacity (the kernel's ``capacity[inst]`` branch and its quantised
+    load bound): demands and capacity scaled by 8 (exact in f32) give the same search, with a
+    [LB, 1] capacity, on one instance per row and on 5 instances shared by 15 rows."""
+    for b, n, cap, lb in ((64, 20, 30, None), (15, 12, 20, 5)):
+        locs, demand, tours, ref, sweeps, _ = tc.uniform_case(b, n, cap, 1000, lb)
+        capacity = np.full((lb or b, 1), 8.0, dtype=np.float32)
+        scaled = demand * np.float32(8)
+        D = [dist_from_locs(l) for l in locs]
+        want = tc.solve(D, scaled, tours, 1000, capacity[:, 0])
+        _eq(want[:2], (ref, sweeps))  # the restatement itself
+        _eq(tc.run(ops.cvrp_local_search, tours, scaled, locs=locs, capacity=capacity,
+                   device=dev), (ref, sweeps))
+        assert (sweeps > 1).any()
 
 
 def test_invalid_rows_set_status_and_the_rest_is_improved(dev):

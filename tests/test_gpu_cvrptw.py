@@ -4,7 +4,12 @@ restatement tests/cvrptw_ref.py bit for bit on every output, over the sizes at w
 kernel takes another path -- N + 1 below, at and above a lane group's two columns per lane
 (N = 63, 64, 70), more columns per lane (N = 200), a single customer, and batches of 1, 3, 16
 and 257 rows (a partial group, a partial wave, more than one workgroup) -- with i32, f32 and
-i64 windows, the hand-made rows, and the kernel edges.  Only the archive is read, never a
+i64 windows, the hand-made rows, and the kernel edges.  N + 1 on both sides of every switch
+of tw_launch (N = 15, 16, 31, 32, 62 with 63 and 64 above, 127, 128, 255, 256, 511, 512; B =
+3), directed rollouts at N = 128, 256, 300, 512, 1023 (B = 4) in which every register slot is
+the action's at least once and column N is visited, and co_cvrptw_check on 300 rows (a second
+block with a partial tail), step-major and row-major actions, every status bit alone in row
+280 and the depot-return bound read from batch row 0.  Only the archive is read, never a
 reference checkout."""
 import pytest
 import torch
@@ -32,6 +37,21 @@ def test_device_matches_the_restatement(n, b):
 def test_rows_of_many_columns_per_lane(n, b):
     """N = 300 and the largest N the entries take, 1023 (CO_CVRPTW_MAX_N)."""
     cc.check_shape(n, b, torch.int32, DEV)
+
+
+@pytest.mark.parametrize("n", cc.SWITCH_SIZES)
+def test_both_sides_of_every_launch_switch(n):
+    """N + 1 below and at 16, 32, 64 (lanes per row) and 128, 256, 512 (columns per lane)."""
+    cc.check_shape(n, 3, cc.TW_DTYPES[cc.SWITCH_SIZES.index(n) % 3], DEV)
+
+
+@pytest.mark.parametrize("n,b", cc.DIRECTED_SHAPES)
+def test_every_register_slot_is_the_action(n, b):
+    """The directed rollout: every register slot a row's lanes hold is the action's at
+    least once and column N is visited -- asserted from the restatement before any kernel
+    is compared -- through single steps and co_cvrptw_steps in both action layouts."""
+    cc.check_directed_inputs(n, b)
+    cc.check_shape(n, b, torch.int32, DEV, directed=True)
 
 
 @pytest.mark.parametrize("dtype", cc.TW_DTYPES)
@@ -69,6 +89,10 @@ def test_check_bits_on_the_device():
     a2[1, 0] = n + 1
     assert cc.abi_check(locs, a2, dur, tw) == 8
     assert cc.abi_check(locs, acts, dur.long(), tw.long()) == 0
+
+
+def test_check_bits_over_two_blocks_on_the_device():
+    cc.check_check_bits_two_blocks(DEV)
 
 
 def test_decode_loops_on_the_device():

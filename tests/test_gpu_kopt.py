@@ -4,8 +4,11 @@ within 1e-5 relative) and co_tsp_kopt_steps against the single-step launches (ev
 bit for bit), over the sizes at which the kernel takes another path: N below, at and above
 the wave width, N = 1024, batches of 1, 3 and 67 rows (more than one block per CU is not
 needed: rows are independent), strided and step-major actions, locs_batch < batch, node 0
-inside the reversed path, the whole-tour reversal and first == second.  Invalid rows only
-set their status bit."""
+inside the reversed path, the whole-tour reversal and first == second.  k_max = 2, 3, 4 at
+every shape and 5, 8, 15, 16 (CO_KOPT_MAX_K) at N = 20, 65, 130 with B = 8, T = 3, the 48-wide
+row of k = 16 also with act_stride_a = 2 and from a padded buffer, and a walk at k = 16 whose
+result is no cycle.  Every (first, second) of one tour at N = 3..6, 65 and 129.  Invalid rows
+only set their status bit."""
 import pytest
 import torch
 
@@ -61,6 +64,48 @@ def test_device_against_host_and_fused_against_single(n, b, k):
         check_equal(got, torch.stack(r1).cpu(), f"T{steps} rewards")
         for key in kc.STATE_INT + kc.STATE_F32:
             check_equal(many[key], one[key].cpu(), f"n{n} b{b} k{k} T{steps} {key}")
+
+
+@pytest.mark.parametrize("k,n", kc.HIGH_K)
+def test_k_max_up_to_the_largest(k, n):
+    """5 <= k_max <= CO_KOPT_MAX_K (16: kopt_walk fills the 16 ints of its right-node scratch,
+    the last bytes of the workgroup's LDS, and the action row is 48 wide), compared as
+    test_device_against_host_and_fused_against_single compares k = 2..4; every row moves and
+    every improvement test is clear of the summation order (kc.high_k_case)."""
+    locs, rec, acts, after = kc.high_k_case(k, n)
+    assert (after[-1]["rec_current"] != rec).any(1).all(), "a row's tour did not change"
+    host_env, dev_env = kc.product_env(n, k, "cpu"), kc.product_env(n, k, DEV)
+    host, _, _ = _run_single(host_env, kc.product_state(locs, rec, "cpu"), acts)
+    dacts = acts.to(DEV)
+    dev, rewards, _ = _run_single(dev_env, kc.product_state(locs, rec, DEV), dacts)
+    for key in kc.STATE_INT:
+        check_equal(dev[key], host[key], f"n{n} k{k} {key}")
+    for key in kc.STATE_F32 + ("reward",):
+        check_close(dev[key], host[key], f"n{n} k{k} {key}")
+    kc.check_state(dev, after[-1], f"n{n} k{k} restatement", kc.STEP_KEYS)
+    check_equal(ImprovementEnvBase._get_real_solution(dev["rec_current"]),
+                kopt_ref.real_solution(host["rec_current"]), "real solution")
+    for steps in (1, 2, 3):
+        one, r1, _ = _run_single(dev_env, kc.product_state(locs, rec, DEV), dacts[:steps])
+        many = kc.product_state(locs, rec, DEV)
+        got = dev_env.improve_steps(many, dacts[:steps])
+        check_equal(got, torch.stack(r1).cpu(), f"T{steps} rewards")
+        for key in kc.STATE_INT + kc.STATE_F32:
+            check_equal(many[key], one[key].cpu(), f"n{n} k{k} T{steps} {key}")
+    if k == 16:  # the 48-wide action row read with act_stride_a != 1 and from a padded buffer
+        t, b, a_w = acts.shape
+        wide = torch.full((t, b, 2 * a_w + 5), -9, dtype=torch.int64, device=DEV)
+        wide[:, :, 3:3 + 2 * a_w:2] = dacts
+        padded = torch.full((t, b, a_w + 5), -9, dtype=torch.int64, device=DEV)
+        padded[:, :, 2:2 + a_w] = dacts
+        for name, view in (("stride 2", wide[:, :, 3:3 + 2 * a_w:2]),
+                           ("padded", padded[:, :, 2:2 + a_w])):
+            assert not view.is_contiguous() and torch.equal(view, dacts)
+            td = kc.product_state(locs, rec, DEV)
+            check_equal(dev_env.improve_steps(td, view), got.cpu(), name + " rewards")
+            for key in kc.STATE_INT + kc.STATE_F32:
+                check_equal(td[key], many[key].cpu(), f"n{n} k16 {name} {key}")
+        assert wide.stride(2) == 1 and wide[:, :, 3:3 + 2 * a_w:2].stride(2) == 2
 
 
 @pytest.mark.parametrize("k", [2, 3])
@@ -127,15 +172,14 @@ def test_two_opt_special_moves(n):
     assert int(td["visited_time"][2, int(rec[2, 0])]) != 1  # node 0 was inside the path
 
 
-@pytest.mark.parametrize("n", [3, 4, 5, 6])
+@pytest.mark.parametrize("n", kc.PAIR_SIZES)
 def test_every_two_opt_pair_on_the_device(n):
     """Every (first, second) of a seeded tour in one launch (B = N * N): the kernel's closed
-    form from positions against the restatement's walk and the host build."""
-    pairs = torch.tensor([(f, s) for f in range(n) for s in range(n)])
+    form from positions against the restatement's walk and the host build.  N = 65 and 129
+    (B = 4225 and 16641) make the second and third trip of the 64-wide loops with every
+    (pos[first], path length), wraps past position N - 1 with node 0 inside included."""
+    pairs, locs, rec, want = kc.all_pairs(n)
     b = pairs.shape[0]
-    locs, rec, _ = kc.instance(1, n, 40 + n)
-    locs, rec = locs.expand(b, n, 2).contiguous(), rec.expand(b, n).contiguous()
-    want = kopt_ref.step(kopt_ref.reset(locs, rec.clone()), pairs, 2)
     host = kc.product_state(locs, rec, "cpu")
     host["action"] = pairs
     host = kc.product_env(n, 2, "cpu").step(host)["next"]
@@ -166,7 +210,7 @@ def test_small_tours_run_real_kopt_moves(k):
         kc.check_state(td, want, f"k{k} n{n}")
 
 
-@pytest.mark.parametrize("k,n", [(3, 6), (4, 70)])
+@pytest.mark.parametrize("k,n", [(3, 6), (4, 70), (16, 70)])
 def test_kopt_result_that_is_no_cycle_sets_invalid_tour(k, n):
     """rec[a] = a (index = left = right = a) is a self loop: kopt_walk's result is not one
     N-cycle.  Only row 1 is spoilt; through the C ABI the bit is set and the other rows'

@@ -2,7 +2,11 @@
 is held to the recording of the reference's own CVRPTWEnv (tests/golden/cvrptw/
 ref_cvrptw.npz: masks, visited sets, nodes, capacities and coordinates bit for bit,
 ``distances`` / ``current_time`` / ``get_reward`` within the project's 1e-5 relative) and,
-bit for bit on every output, to the restatement tests/cvrptw_ref.py written from the header;
+bit for bit on every output, to the restatement tests/cvrptw_ref.py written from the header
+(N + 1 on both sides of every lane-group and columns-per-lane switch of the kernel: N = 15,
+16, 31, 32, 62, 63, 64, 127, 128, 255, 256, 511, 512; directed rollouts at N = 128, 256, 300,
+512, 1023 in which every register slot is the action's and column N is visited; the check
+entry on 300 rows with every status bit alone in row 280);
 the generator reproduces the reference's draws; and the Python surface (registry, td
 contract, decode loops on the two-call path, ``improve``, Solomon dicts, bindings) is
 checked.  tests/test_gpu_cvrptw.py runs the same checks on the device."""
@@ -92,6 +96,21 @@ def test_rows_of_many_columns_per_lane(n, b):
     cc.check_shape(n, b, torch.int32, "cpu")
 
 
+@pytest.mark.parametrize("n", cc.SWITCH_SIZES)
+def test_both_sides_of_every_launch_switch(n):
+    """N + 1 below and at 16, 32, 64 (lanes per row) and 128, 256, 512 (columns per lane)."""
+    cc.check_shape(n, 3, cc.TW_DTYPES[cc.SWITCH_SIZES.index(n) % 3], "cpu")
+
+
+@pytest.mark.parametrize("n,b", cc.DIRECTED_SHAPES)
+def test_every_register_slot_is_the_action(n, b):
+    """The directed rollout: every register slot a row's lanes hold is the action's at
+    least once and column N is visited -- asserted from the restatement before any kernel
+    is compared -- through single steps and co_cvrptw_steps in both action layouts."""
+    cc.check_directed_inputs(n, b)
+    cc.check_shape(n, b, torch.int32, "cpu", directed=True)
+
+
 @pytest.mark.parametrize("dtype", cc.TW_DTYPES)
 def test_window_dtypes(dtype):
     cc.check_shape(20, 16, dtype, "cpu")
@@ -146,6 +165,10 @@ def test_check_bits_match_the_restatement():
     assert both(dur, tw, a2) == nat.ST_INDEX_RANGE
     for dt in (torch.float32, torch.int64):
         assert both(dur.to(dt), tw.to(dt)) == 0
+
+
+def test_check_bits_over_two_blocks():
+    cc.check_check_bits_two_blocks("cpu")
 
 
 def test_registry_bindings_and_td_contract():

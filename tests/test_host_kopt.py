@@ -2,7 +2,8 @@
 restatement tests/kopt_ref.py and the host build of the C ABI are held to the recording of
 the reference's own TSPkoptEnv (tests/golden/kopt/ref_kopt.npz: integers bit for bit, costs
 and rewards within the project's 1e-5 relative), the host build to the restatement on every
-2-opt pair of small tours, and the Python surface (registry, td contract, in-place
+2-opt pair of one tour at N = 3..6, 65 and 129 and on k_max = 5, 8, 15, 16 (CO_KOPT_MAX_K) at
+N = 20, 65, 130, and the Python surface (registry, td contract, in-place
 ``rec_best``, status bits, argument errors, bindings) is checked."""
 import os
 import re
@@ -99,16 +100,14 @@ def test_recording_is_what_the_reference_returns(tmp_path):
             assert (new[key] == old[key]).all(), key
 
 
-@pytest.mark.parametrize("n", [3, 4, 5, 6])
+@pytest.mark.parametrize("n", kc.PAIR_SIZES)
 def test_every_two_opt_pair(n):
-    """Every (first, second) on a seeded tour: the host build against the restatement."""
-    pairs = torch.tensor([(f, s) for f in range(n) for s in range(n)])
-    b = pairs.shape[0]
-    locs, rec, _ = kc.instance(1, n, 40 + n)
-    locs, rec = locs.expand(b, n, 2).contiguous(), rec.expand(b, n).contiguous()
+    """Every (first, second) on a seeded tour: the host build against the restatement.  At
+    N = 65 and 129 every (pos[first], path length) occurs with the path wrapping past
+    position N - 1 and node 0 inside it."""
+    pairs, locs, rec, want = kc.all_pairs(n)
     env = kc.product_env(n, 2, "cpu")
     td = kc.product_state(locs, rec, "cpu")
-    want = kopt_ref.step(kopt_ref.reset(locs, rec.clone()), pairs, 2)
     assert kopt_ref.is_cycle(want["rec_current"]).all()
     td["action"] = pairs
     td = env.step(td)["next"]
@@ -151,6 +150,30 @@ def test_improve_steps_equals_single_steps(k, n, t):
         check_equal(got, torch.stack(rewards), "rewards")
         want, _ = kopt_ref.steps(kopt_ref.reset(locs, rec.clone()), acts, k)
         kc.check_state(many, want, f"k{k} n{n} restatement")
+
+
+@pytest.mark.parametrize("k,n", kc.HIGH_K)
+def test_k_max_up_to_the_largest_against_the_restatement(k, n):
+    """5 <= k_max <= CO_KOPT_MAX_K (16: all of the walk's right-node scratch, an action row
+    48 wide): single steps and improve_steps against the restatement; every row moves."""
+    locs, rec, acts, after = kc.high_k_case(k, n)
+    assert acts.shape == (3, 8, 3 * k)
+    assert (after[-1]["rec_current"] != rec).any(1).all(), "a row's tour did not change"
+    env = kc.product_env(n, k, "cpu")
+    td = kc.product_state(locs, rec, "cpu")
+    rewards = []
+    for t, a in enumerate(acts):
+        td["action"] = a
+        td = env.step(td)["next"]
+        kc.check_state(td, after[t], f"k{k} n{n} step {t}", kc.STEP_KEYS)
+        rewards.append(td["reward"])
+    many = kc.product_state(locs, rec, "cpu")
+    got = env.improve_steps(many, acts)
+    kc.check_state(many, after[-1], f"k{k} n{n} improve_steps")
+    check_close(got, torch.stack([s["reward"] for s in after]), "rewards")
+    check_equal(got, torch.stack(rewards), "fused against single rewards")
+    for key in kc.STATE_INT + kc.STATE_F32:
+        check_equal(many[key], td[key], f"k{k} n{n} fused against single {key}")
 
 
 def test_registry_and_td_contract():
@@ -234,6 +257,15 @@ def test_status_bits_and_messages():
     td["action"] = torch.cat((a, a, a), 1).expand(3, 9)  # rec[0] = 0: a self loop
     with pytest.raises(AssertionError, match="Not visiting all nodes"):
         env3.step(td)
+    # the same at k_max = CO_KOPT_MAX_K, one row spoilt
+    locs, rec, g = kc.instance(3, 20, 9)
+    acts = kc.kopt_actions(g, rec, 16, 1)[0]
+    acts[1] = 2
+    assert kopt_ref.is_cycle(kopt_ref.k_opt(rec, acts, 16)).tolist() == [True, False, True]
+    td = kc.product_state(locs, rec, "cpu")
+    td["action"] = acts
+    with pytest.raises(AssertionError, match="Not visiting all nodes"):
+        kc.product_env(20, 16, "cpu").step(td)
 
 
 def test_argument_errors_and_the_empty_batch():
@@ -268,6 +300,14 @@ def test_header_native_and_fastcall_bindings():
         assert hasattr(nat.load_host(), name)
     assert f"#define CO_KOPT_MAX_N {nat.KOPT_MAX_N}" in header
     assert f"#define CO_KOPT_MAX_K {nat.KOPT_MAX_K}" in header
+    # k_max = CO_KOPT_MAX_K is taken and one more is CO_E_INVAL: decided before the empty
+    # batch returns and before any launch, so the device library answers without a device
+    assert nat.KOPT_MAX_K == 16
+    p = torch.zeros(64, dtype=torch.int64).data_ptr()
+    for lib in (nat.load_host(), nat.load()):
+        for k, want in ((2, 0), (nat.KOPT_MAX_K, 0), (nat.KOPT_MAX_K + 1, -1), (1, -1)):
+            assert lib.co_tsp_kopt_steps(0, 5, k, 1, None, 1, None, 0, 0, 0, *([None] * 10)) == want
+            assert lib.co_tsp_kopt_step(0, 5, k, None, 1, None, p, 0, 0, *([None] * 11)) == want
     fast = nat._fastcall()
     assert fast is not None
     for name in KOPT_SYMBOLS:
