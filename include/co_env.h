@@ -955,6 +955,166 @@ int co_cvrptw_steps(int64_t batch, int64_t num_loc, int64_t steps, const int64_t
                     uint8_t* feasible, float* time, int32_t* status, int32_t* not_done,
                     void* stream);
 
+/* ---------------------------------------------------------------- MTVRP */
+
+/* The multi-task VRP (rl4co/envs/routing/mtvrp/env.py): capacity plus any combination of
+ * open routes (O), backhauls (B), a route-length limit (L) and time windows (TW), each row of
+ * a batch its own variant.  N = customers, NC = N + 1 columns (the depot first), 1 <= N <=
+ * CO_MTVRP_MAX_N, else CO_E_INVAL; an empty batch is a no-op; a NULL pointer not marked
+ * nullable is CO_E_INVAL; locs and time_windows hold pairs and must be 8-byte aligned
+ * (CO_E_ALIGN).
+ *
+ * Inputs, all f32 but the two byte arrays: locs [B, NC, 2]; time_windows [B, NC, 2] (start,
+ * end; +inf end = no window); service_time, demand_linehaul, demand_backhaul [B, NC] (0 at the
+ * depot); the per-row scalars vehicle_capacity, speed, distance_limit (+inf = no limit) [B, 1]
+ * and open_route [B, 1] (u8, != 0 is open) -- taken from the td, not from the generator.
+ * State: current_node [B] i64; current_time, current_route_length, used_capacity_linehaul,
+ * used_capacity_backhaul [B, 1] f32; visited [B, NC] u8.
+ *
+ * Arithmetic.  Every operation is f32, each rounded on its own (no FMA, no fast-math,
+ * correctly rounded sqrtf and /).  dist(p, q) is the CVRPTW section's sqrtf(dx*dx + dy*dy),
+ * with the same one-ulp deviation from torch's norm.  A bool times a float is a
+ * multiplication by 0.0f / 1.0f, so 0 * NaN and 0 * inf are NaN.  max is torch.max: NaN
+ * when either operand is NaN.  Every compare is false for a NaN.
+ *
+ * The mask of a state (get_action_mask, env.py:212-279), with cur = clamp(current_node, 0,
+ * N) for the coordinates, nopen = (float)!open_route, per column c = 0..N:
+ *   d_ij[c]  = dist(locs[cur], locs[c])                                        :215-217
+ *   d_j0[c]  = dist(locs[c], locs[0])                                          :218
+ *   arr      = current_time + d_ij[c] / speed                                  :225
+ *   reach    = arr < tw[c][1]                                                  :227
+ *   depot_ok = ((max(arr, tw[c][0]) + service[c]) + d_j0[c] / speed) * nopen
+ *              < tw[0][1]                                                      :230-232
+ *   over     = (route_len + d_ij[c]) + d_j0[c] * nopen > distance_limit        :235-238
+ *   lh_missing   = some unvisited column has demand_linehaul > 0               :242-244
+ *   carrying_bh  = demand_backhaul[cur] > 0                                    :245-253
+ *   demand_ok = (lh_missing && !(dl[c] + used_l > cap) && !carrying_bh && dl[c] > 0)
+ *               || (!(db[c] + used_b > cap) && db[c] > 0)                      :254-266
+ *   can[c]   = reach && depot_ok && demand_ok && !over && !visited[c]          :269-275
+ *   can[0]   = !(current_node == 0 && any(can[1..N]))                          :278
+ * The depot column ignores every other test.  lh_missing: the reference's sum(dl *
+ * !visited) > 0 is exactly this for finite non-negative demands; a NaN, infinite or negative
+ * linehaul demand makes the reference's sum differ (NaN: never missing), which is not
+ * reproduced.
+ *
+ * The step (env.py:100-162), a = action[b]; an a outside 0..N sets CO_ST_INDEX_RANGE and
+ * leaves the row's whole state (node, time, length, capacities, visited) as it was:
+ *   leg = dist(locs[cur], locs[a])           -- recomputed, no stored distances vector
+ *   current_time         = (float)(a != 0) * (max(current_time + leg / speed, tw[a][0])
+ *                          + service[a])                                       :115-118
+ *   current_route_length = (float)(a != 0) * (route_len + leg)                 :121-123
+ *   used_l = (float)(a != 0) * (used_l + dl[a]); used_b likewise with db       :135-140
+ *   visited[a] = 1; done = sum(visited) == NC; reward = 0.0f; current_node = a :143-147
+ *   then the mask above on the new state.
+ *
+ * The reward (env.py:281-291): the legs depot -> a_0 -> ... -> a_{T-1} -> depot, a leg whose
+ * destination is the depot counting 0 on an open row, summed in f64 in step order and
+ * rounded once, negated (as co_cvrp_reward accumulates; 1e-5 relative to the reference, not
+ * bit for bit).  An a outside 0..N sets CO_ST_INDEX_RANGE; its two legs are left out.
+ *
+ * Validity (check_solution_validity, env.py:294-365), one status bit per message, in the
+ * reference's order; d0[c] = dist(locs[c], locs[0]):
+ *   not (every customer exactly once, every other entry 0)      CO_ST_INVALID_TOUR     :301-306
+ *   !(distance_limit >= 0)                                      CO_ST_MT_LIMIT_NEGATIVE   :309
+ *   !(tw >= 0) (either end)                                     CO_ST_MT_TW_NEGATIVE      :313
+ *   !(service >= 0)                                             CO_ST_MT_SERVICE_NEGATIVE :314
+ *   !(tw[c][0] < tw[c][1])                                      CO_ST_MT_TW_INFEASIBLE :315-317
+ *   !((tw[c][0] + d0[c]) + service[c] <= tw[0][1])              CO_ST_MT_DEPOT_RETURN  :318-321
+ *       -- the bound is THIS ROW's depot deadline (the reference's indexing gives that here,
+ *       unlike CVRPTW's batch row 0)
+ *   the scan from the depot, len = t = 0, per action a (an a outside 0..N: CO_ST_INDEX_RANGE
+ *   and CO_ST_INVALID_TOUR, no scan for the row), d = dist(locs[prev], locs[a]):
+ *     len = len + d * (float)!(open && a == 0); !(len <= distance_limit)
+ *                                                               CO_ST_MT_ROUTE_LIMIT   :333-338
+ *     len = 0 when a == 0
+ *     t = max(t + d, tw[a][0]); !(t <= tw[a][1])                CO_ST_MT_DEADLINE      :341-346
+ *     t = t + service[a]; t = 0 when a == 0
+ *       -- the scan adds d itself, not d / speed, and resets at the depot: as the reference
+ *     ul = ul * (float)(a != 0) + dl[a]; !(ul <= cap)           CO_ST_MT_OVER_LINEHAUL :353-364
+ *     ub likewise with db                                       CO_ST_MT_OVER_BACKHAUL
+ *       -- against this row's vehicle_capacity (the reference broadcasts [B] against [B, 1]
+ *       and so compares with every row's; equal when all capacities are, as generated) */
+#define CO_MTVRP_MAX_N 1023
+
+/* The instance inputs above, one pointer each, handed to every MTVRP entry but the reward
+ * as one table in host memory; it is read during the call and need not outlive it.  A NULL
+ * table or member is CO_E_INVAL (co_mtvrp_check does not read speed, which may be NULL). */
+typedef struct co_mtvrp_instance {
+  const float* locs;             /* [B, NC, 2], 8-byte aligned */
+  const float* time_windows;     /* [B, NC, 2], 8-byte aligned */
+  const float* service_time;     /* [B, NC] */
+  const float* demand_linehaul;  /* [B, NC] */
+  const float* demand_backhaul;  /* [B, NC] */
+  const float* vehicle_capacity; /* [B, 1] */
+  const float* speed;            /* [B, 1] */
+  const float* distance_limit;   /* [B, 1] */
+  const uint8_t* open_route;     /* [B, 1] */
+} co_mtvrp_instance;
+
+#define CO_ST_MT_LIMIT_NEGATIVE 2048     /* "Distance limits must be non-negative." */
+#define CO_ST_MT_TW_NEGATIVE 4096        /* "Time windows must be non-negative." */
+#define CO_ST_MT_SERVICE_NEGATIVE 8192   /* "Service time must be non-negative." */
+#define CO_ST_MT_TW_INFEASIBLE 16384     /* "there are unfeasible time windows" */
+#define CO_ST_MT_DEPOT_RETURN 32768      /* "vehicle cannot perform service and get back to
+                                            depot in time." */
+#define CO_ST_MT_ROUTE_LIMIT 65536       /* "Route exceeds distance limit" */
+#define CO_ST_MT_DEADLINE 131072         /* "vehicle cannot start service before deadline" */
+#define CO_ST_MT_OVER_LINEHAUL 262144    /* "Used more than capacity for demand_linehaul" */
+#define CO_ST_MT_OVER_BACKHAUL 524288    /* "Used more than capacity for demand_backhaul" */
+
+/* MTVRPEnv._reset (env.py:164-209) in one launch: the zeroed state at the depot and its
+ * mask. */
+int co_mtvrp_reset(int64_t batch, int64_t num_loc, const co_mtvrp_instance* instance,
+                   int64_t* current_node, float* current_time, float* current_route_length,
+                   float* used_linehaul, float* used_backhaul, uint8_t* visited,
+                   uint8_t* action_mask, void* stream);
+
+/* MTVRPEnv._step (env.py:100-162) in one launch: the update and the new mask.  Every output
+ * is a buffer of its own, but visited_out may be visited_in.  status / not_done (nullable)
+ * as in co_cvrptw_step.  One step moves 31 NC + 70 bytes per row (locs 8, windows 8,
+ * service 4, two demands 8, visited 1 in and 1 out, the mask 1 per column; 70 of row
+ * scalars) against 2 NC square roots and 2 NC divisions: bandwidth-bound. */
+int co_mtvrp_step(int64_t batch, int64_t num_loc, const int64_t* action, const co_mtvrp_instance* instance,
+                  const int64_t* current_in, const float* time_in, const float* route_length_in,
+                  const float* used_linehaul_in, const float* used_backhaul_in,
+                  const uint8_t* visited_in, int64_t* current_out, float* time_out,
+                  float* route_length_out, float* used_linehaul_out, float* used_backhaul_out,
+                  uint8_t* visited_out, uint8_t* done, float* reward, uint8_t* action_mask,
+                  int32_t* status, int32_t* not_done, void* stream);
+
+/* MTVRPEnv.get_action_mask alone (env.py:212-279). */
+int co_mtvrp_action_mask(int64_t batch, int64_t num_loc, const co_mtvrp_instance* instance,
+                         const int64_t* current_node, const float* current_time,
+                         const float* current_route_length, const float* used_linehaul,
+                         const float* used_backhaul, const uint8_t* visited,
+                         uint8_t* action_mask, void* stream);
+
+/* `steps` (>= 1) preset co_mtvrp_step calls in one launch: action (t, b) at
+ * actions[t*act_stride_t + b*act_stride_b].  The state is updated in place; done, reward and
+ * action_mask are written for the last step, the mask computed once, on the final state,
+ * which is that of the `steps` single calls bit for bit.  Nullable per-step outputs, [steps,
+ * B]: feasible (u8: the value action_mask[b, a_t] had before step t; 0 for an a_t outside
+ * 0..N), time and route_length (f32: current_time / current_route_length after step t).
+ * not_done counts the rows not done after the last step.  On the device the row stays in
+ * registers for the whole call. */
+int co_mtvrp_steps(int64_t batch, int64_t num_loc, int64_t steps, const int64_t* actions,
+                   int64_t act_stride_t, int64_t act_stride_b, const co_mtvrp_instance* instance,
+                   int64_t* current_node, float* current_time, float* current_route_length,
+                   float* used_linehaul, float* used_backhaul, uint8_t* visited, uint8_t* done,
+                   float* reward, uint8_t* action_mask, uint8_t* feasible, float* time,
+                   float* route_length, int32_t* status, int32_t* not_done, void* stream);
+
+/* MTVRPEnv._get_reward for actions [B, T] (element (b, t) at b*act_stride_b +
+ * t*act_stride_t), as stated above; status nullable. */
+int co_mtvrp_reward(int64_t batch, int64_t num_loc, int64_t steps, const float* locs,
+                    const int64_t* actions, int64_t act_stride_b, int64_t act_stride_t,
+                    const uint8_t* open_route, float* reward, int32_t* status, void* stream);
+
+/* check_solution_validity for actions [B, T]: the status bits stated above. */
+int co_mtvrp_check(int64_t batch, int64_t num_loc, int64_t steps,
+                   const co_mtvrp_instance* instance, const int64_t* actions,
+                   int64_t act_stride_b, int64_t act_stride_t, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

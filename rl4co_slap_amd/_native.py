@@ -102,6 +102,13 @@ _SIGS = {
     "co_cvrptw_check": [_i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i32, _p, _i32, _p, _p],
     "co_cvrptw_steps": [_i64, _i64, _i64, _p, _i64, _i64] + [_p] * 9 + [_i32, _p, _i32]
                        + [_p] * 10,
+    # the co_mtvrp_instance table (mtvrp_instance below) is one pointer argument
+    "co_mtvrp_reset": [_i64, _i64] + [_p] * 9,
+    "co_mtvrp_step": [_i64, _i64] + [_p] * 20,
+    "co_mtvrp_action_mask": [_i64, _i64] + [_p] * 9,
+    "co_mtvrp_steps": [_i64, _i64, _i64, _p, _i64, _i64] + [_p] * 16,
+    "co_mtvrp_reward": [_i64, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p],
+    "co_mtvrp_check": [_i64, _i64, _i64, _p, _p, _i64, _i64, _p, _p],
 }
 
 ST_INVALID_TOUR = 1
@@ -113,6 +120,11 @@ ST_LOGP_NEG_INF = 32
 # CO_ST_TW_*: co_cvrptw_check's bits, one per message of the reference's check
 ST_TW_NEGATIVE, ST_TW_DEPOT_RETURN, ST_DURATION_NEGATIVE = 64, 128, 256
 ST_TW_INFEASIBLE, ST_TW_DEADLINE = 512, 1024
+# CO_ST_MT_*: co_mtvrp_check's bits, one per message of the reference's check
+ST_MT_LIMIT_NEGATIVE, ST_MT_TW_NEGATIVE, ST_MT_SERVICE_NEGATIVE = 2048, 4096, 8192
+ST_MT_TW_INFEASIBLE, ST_MT_DEPOT_RETURN, ST_MT_ROUTE_LIMIT = 16384, 32768, 65536
+ST_MT_DEADLINE, ST_MT_OVER_LINEHAUL, ST_MT_OVER_BACKHAUL = 131072, 262144, 524288
+MTVRP_MAX_N = 1023  # CO_MTVRP_MAX_N: the most customers the MTVRP entries take
 CVRPTW_MAX_N = 1023  # CO_CVRPTW_MAX_N: the most customers the CVRPTW entries take
 DT_F32, DT_I32, DT_I64 = 0, 1, 2  # CO_DT_*: dtype codes of durations / time_windows
 DECODE_FAST = 0x100  # CO_DECODE_FAST mode flag (opt-in fast math; not bit-exact)
@@ -193,6 +205,8 @@ HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt"
                 "co_cvrp_local_search",
                 "co_cvrptw_reset", "co_cvrptw_step", "co_cvrptw_action_mask", "co_cvrptw_check",
                 "co_cvrptw_steps",
+                "co_mtvrp_reset", "co_mtvrp_step", "co_mtvrp_action_mask", "co_mtvrp_steps",
+                "co_mtvrp_reward", "co_mtvrp_check",
                 "co_slap_reset", "co_slap_step", "co_slap_reward", "co_slap_local_search",
                 "co_gather_by_index", "co_best_of", "co_tsp_best_of",
                 "co_decode_step"]
@@ -258,6 +272,25 @@ def exported_symbols():
 
 def ptr(t):
     return None if t is None else t.data_ptr()
+
+
+class MtvrpInstance(ctypes.Structure):
+    """``co_mtvrp_instance`` (include/co_env.h): the MTVRP instance pointers as one table."""
+    FIELDS = ("locs", "time_windows", "service_time", "demand_linehaul", "demand_backhaul",
+              "vehicle_capacity", "speed", "distance_limit", "open_route")
+    _fields_ = [(name, ctypes.c_void_p) for name in FIELDS]
+
+    @property
+    def address(self) -> int:
+        """What a call passes; the table must stay referenced until the call returns."""
+        return ctypes.addressof(self)
+
+
+def mtvrp_instance(*tensors) -> MtvrpInstance:
+    """The table of the nine instance tensors, in ``MtvrpInstance.FIELDS`` order (None: a
+    NULL member)."""
+    assert len(tensors) == len(MtvrpInstance.FIELDS)
+    return MtvrpInstance(*(ptr(t) for t in tensors))
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)

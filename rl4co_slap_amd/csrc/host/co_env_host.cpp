@@ -1566,6 +1566,287 @@ CO_HOST_API int co_cvrptw_steps(int64_t B, int64_t N, int64_t T, const int64_t* 
   return CO_OK;
 }
 
+// -------------------------------------------------------------------------- MTVRP
+// mtvrp/env.py in its plain scalar form; co_env.h states the semantics.  co_mtvrp_steps is
+// literally `steps` single steps per row, each followed by its full mask.
+namespace {
+struct MtInst {  // one row's inputs
+  int64_t N;
+  const float *lr, *tw, *svc, *dl, *db;
+  float cap, speed, limit, nopen;
+};
+struct MtState {
+  int64_t cur;
+  float t, len, ul, ub;
+};
+inline bool mt_sizes_ok(int64_t B, int64_t N) { return B >= 0 && N > 0 && N <= CO_MTVRP_MAX_N; }
+
+inline MtInst mt_row(int64_t N, int64_t b, const co_mtvrp_instance* in) {
+  const int64_t NC = N + 1;
+  return MtInst{N, in->locs + 2 * b * NC, in->time_windows + 2 * b * NC,
+                in->service_time + b * NC, in->demand_linehaul + b * NC,
+                in->demand_backhaul + b * NC, in->vehicle_capacity[b],
+                in->speed ? in->speed[b] : 1.f, in->distance_limit[b],
+                in->open_route[b] != 0 ? 0.0f : 1.0f};
+}
+// every member but (with_speed = false: co_mtvrp_check) speed is there
+inline bool mt_inst_ok(const co_mtvrp_instance* in, bool with_speed = true) {
+  return in && in->locs && in->time_windows && in->service_time && in->demand_linehaul &&
+         in->demand_backhaul && in->vehicle_capacity && (in->speed || !with_speed) &&
+         in->distance_limit && in->open_route;
+}
+
+// get_action_mask (mtvrp/env.py:212-279) of one row
+void mt_mask_row(const MtInst& in, const MtState& s, const uint8_t* vis, uint8_t* mask) {
+  const int64_t N = in.N;
+  const int64_t cc = s.cur < 0 ? 0 : (s.cur > N ? N : s.cur);
+  const float cx = in.lr[2 * cc], cy = in.lr[2 * cc + 1], twe0 = in.tw[1];
+  bool lhm = false;
+  for (int64_t c = 0; c <= N; ++c) lhm = lhm || (!vis[c] && in.dl[c] > 0.f);
+  const bool cbh = in.db[cc] > 0.f;
+  bool anyc = false;
+  for (int64_t c = 0; c <= N; ++c) {
+    const float dij = tw_dist(cx, cy, in.lr[2 * c], in.lr[2 * c + 1]);
+    const float dj0 = tw_dist(in.lr[2 * c], in.lr[2 * c + 1], in.lr[0], in.lr[1]);
+    const float arr = s.t + dij / in.speed;
+    const bool reach = arr < in.tw[2 * c + 1];
+    const bool depot_ok =
+        ((tw_max(arr, in.tw[2 * c]) + in.svc[c]) + dj0 / in.speed) * in.nopen < twe0;
+    const bool over = (s.len + dij) + dj0 * in.nopen > in.limit;
+    const bool dem = (lhm && !(in.dl[c] + s.ul > in.cap) && !cbh && in.dl[c] > 0.f) ||
+                     (!(in.db[c] + s.ub > in.cap) && in.db[c] > 0.f);
+    const bool can = reach && depot_ok && dem && !over && !vis[c];
+    mask[c] = can;
+    anyc = anyc || (c >= 1 && can);
+  }
+  mask[0] = !(s.cur == 0 && anyc);
+}
+
+// one step of one row (mtvrp/env.py:100-162); false for an action outside 0..N, which
+// leaves the state as it was
+bool mt_step_row(const MtInst& in, MtState& s, uint8_t* vis, int64_t a) {
+  if (a < 0 || a > in.N) return false;
+  const int64_t cc = s.cur < 0 ? 0 : (s.cur > in.N ? in.N : s.cur);
+  const float leg = tw_dist(in.lr[2 * cc], in.lr[2 * cc + 1], in.lr[2 * a], in.lr[2 * a + 1]);
+  const float m01 = a != 0 ? 1.0f : 0.0f;
+  s.t = m01 * (tw_max(s.t + leg / in.speed, in.tw[2 * a]) + in.svc[a]);
+  s.len = m01 * (s.len + leg);
+  s.ul = m01 * (s.ul + in.dl[a]);
+  s.ub = m01 * (s.ub + in.db[a]);
+  vis[a] = 1;
+  s.cur = a;
+  return true;
+}
+}  // namespace
+
+CO_HOST_API int co_mtvrp_reset(int64_t B, int64_t N, const co_mtvrp_instance* in, int64_t* cur, float* time, float* route_len,
+                               float* used_l, float* used_b, uint8_t* visited, uint8_t* mask,
+                               void*) {
+  if (!mt_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!mt_inst_ok(in) || !cur || !time ||
+      !route_len || !used_l || !used_b || !visited || !mask)
+    return CO_E_INVAL;
+  if (tw_mis8(in->locs) || tw_mis8(in->time_windows)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b) {
+    std::memset(visited + b * NC, 0, (size_t)NC);
+    cur[b] = 0;
+    time[b] = route_len[b] = used_l[b] = used_b[b] = 0.f;
+    mt_mask_row(mt_row(N, b, in),
+                MtState{0, 0.f, 0.f, 0.f, 0.f}, visited + b * NC, mask + b * NC);
+  }
+  return CO_OK;
+}
+
+CO_HOST_API int co_mtvrp_step(int64_t B, int64_t N, const int64_t* action, const co_mtvrp_instance* inst, const int64_t* cur_in,
+                              const float* t_in, const float* len_in, const float* ul_in,
+                              const float* ub_in, const uint8_t* vis_in, int64_t* cur_out,
+                              float* t_out, float* len_out, float* ul_out, float* ub_out,
+                              uint8_t* vis_out, uint8_t* done, float* reward, uint8_t* mask,
+                              int32_t* status, int32_t* not_done, void*) {
+  if (!mt_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!mt_inst_ok(inst) || !action ||
+      !cur_in || !t_in || !len_in || !ul_in || !ub_in || !vis_in || !cur_out || !t_out ||
+      !len_out || !ul_out || !ub_out || !vis_out || !done || !reward || !mask)
+    return CO_E_INVAL;
+  if (tw_mis8(inst->locs) || tw_mis8(inst->time_windows)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  int32_t left = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const MtInst in = mt_row(N, b, inst);
+    uint8_t* vo = vis_out + b * NC;
+    if (vo != vis_in + b * NC) std::memcpy(vo, vis_in + b * NC, (size_t)NC);
+    MtState s{cur_in[b], t_in[b], len_in[b], ul_in[b], ub_in[b]};
+    if (!mt_step_row(in, s, vo, action[b])) set_status(status, CO_ST_INDEX_RANGE);
+    int64_t vsum = 0;
+    for (int64_t c = 0; c < NC; ++c) vsum += vo[c] != 0;
+    cur_out[b] = s.cur, t_out[b] = s.t, len_out[b] = s.len, ul_out[b] = s.ul, ub_out[b] = s.ub;
+    done[b] = vsum == NC;
+    left += vsum != NC;
+    reward[b] = 0.f;
+    mt_mask_row(in, s, vo, mask + b * NC);
+  }
+  if (not_done) *not_done += left;
+  return CO_OK;
+}
+
+CO_HOST_API int co_mtvrp_action_mask(int64_t B, int64_t N, const co_mtvrp_instance* in, const int64_t* cur, const float* time,
+                                     const float* route_len, const float* used_l,
+                                     const float* used_b, const uint8_t* visited, uint8_t* mask,
+                                     void*) {
+  if (!mt_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!mt_inst_ok(in) || !cur || !time ||
+      !route_len || !used_l || !used_b || !visited || !mask)
+    return CO_E_INVAL;
+  if (tw_mis8(in->locs) || tw_mis8(in->time_windows)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b)
+    mt_mask_row(mt_row(N, b, in),
+                MtState{cur[b], time[b], route_len[b], used_l[b], used_b[b]}, visited + b * NC,
+                mask + b * NC);
+  return CO_OK;
+}
+
+CO_HOST_API int co_mtvrp_steps(int64_t B, int64_t N, int64_t T, const int64_t* actions,
+                               int64_t st, int64_t sb, const co_mtvrp_instance* inst, int64_t* cur, float* time_io,
+                               float* route_len, float* used_l, float* used_b, uint8_t* visited,
+                               uint8_t* done, float* reward, uint8_t* mask, uint8_t* feasible,
+                               float* time, float* rlen, int32_t* status, int32_t* not_done,
+                               void*) {
+  if (!mt_sizes_ok(B, N) || T < 1 || T > (1 << 20)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!mt_inst_ok(inst) || !actions ||
+      !cur || !time_io || !route_len || !used_l || !used_b || !visited || !done || !reward ||
+      !mask)
+    return CO_E_INVAL;
+  if (tw_mis8(inst->locs) || tw_mis8(inst->time_windows)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  int32_t left = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const MtInst in = mt_row(N, b, inst);
+    uint8_t *vis = visited + b * NC, *mv = mask + b * NC;
+    MtState s{cur[b], time_io[b], route_len[b], used_l[b], used_b[b]};
+    mt_mask_row(in, s, vis, mv);  // the mask of the input state
+    for (int64_t t = 0; t < T; ++t) {
+      const int64_t a = actions[t * st + b * sb];
+      const bool bad = a < 0 || a > N;
+      if (feasible) feasible[t * B + b] = !bad && mv[a];
+      if (!mt_step_row(in, s, vis, a)) set_status(status, CO_ST_INDEX_RANGE);
+      if (time) time[t * B + b] = s.t;
+      if (rlen) rlen[t * B + b] = s.len;
+      mt_mask_row(in, s, vis, mv);
+    }
+    int64_t vsum = 0;
+    for (int64_t c = 0; c < NC; ++c) vsum += vis[c] != 0;
+    cur[b] = s.cur, time_io[b] = s.t, route_len[b] = s.len, used_l[b] = s.ul, used_b[b] = s.ub;
+    done[b] = vsum == NC;
+    left += vsum != NC;
+    reward[b] = 0.f;
+  }
+  if (not_done) *not_done += left;
+  return CO_OK;
+}
+
+CO_HOST_API int co_mtvrp_reward(int64_t B, int64_t N, int64_t T, const float* locs,
+                                const int64_t* actions, int64_t sb, int64_t st,
+                                const uint8_t* open, float* reward, int32_t* status, void*) {
+  if (!mt_sizes_ok(B, N) || T < 0 || T > (1 << 20)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!locs || (T > 0 && !actions) || !open || !reward) return CO_E_INVAL;
+  if (tw_mis8(locs)) return CO_E_ALIGN;
+  for (int64_t b = 0; b < B; ++b) {
+    const float* lr = locs + 2 * b * (N + 1);
+    const bool op = open[b] != 0;
+    int64_t prev = 0;
+    bool prev_ok = true, range = false;
+    double acc = 0.0;
+    for (int64_t k = 0; k < T; ++k) {
+      const int64_t a = actions[b * sb + k * st];
+      if (a < 0 || a > N) {
+        range = true;
+        prev_ok = false;
+        continue;
+      }
+      if (prev_ok && !(a == 0 && op))
+        acc += (double)tw_dist(lr[2 * prev], lr[2 * prev + 1], lr[2 * a], lr[2 * a + 1]);
+      prev = a;
+      prev_ok = true;
+    }
+    if (prev_ok && !op) acc += (double)tw_dist(lr[2 * prev], lr[2 * prev + 1], lr[0], lr[1]);
+    reward[b] = -(float)acc;
+    if (range) set_status(status, CO_ST_INDEX_RANGE);
+  }
+  return CO_OK;
+}
+
+CO_HOST_API int co_mtvrp_check(int64_t B, int64_t N, int64_t T, const co_mtvrp_instance* inst,
+                               const int64_t* actions, int64_t sb, int64_t st, int32_t* status,
+                               void*) {
+  if (!mt_sizes_ok(B, N) || T < 0 || T > (1 << 20)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!mt_inst_ok(inst, false) || (T > 0 && !actions) || !status) return CO_E_INVAL;
+  if (tw_mis8(inst->locs) || tw_mis8(inst->time_windows)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  std::vector<uint8_t> seen((size_t)NC);
+  for (int64_t b = 0; b < B; ++b) {
+    const MtInst in = mt_row(N, b, inst);
+    int32_t bits = 0;
+    std::fill(seen.begin(), seen.end(), 0);
+    int64_t nonzero = 0;
+    bool range = false, dup = false;
+    for (int64_t k = 0; k < T; ++k) {
+      const int64_t a = actions[b * sb + k * st];
+      if (a < 0 || a > N) {
+        range = true;
+      } else if (a != 0) {
+        ++nonzero;
+        dup = dup || seen[(size_t)a];
+        seen[(size_t)a] = 1;
+      }
+    }
+    if (range) bits |= CO_ST_INDEX_RANGE;
+    if (range || dup || nonzero != N) bits |= CO_ST_INVALID_TOUR;
+    const float twe0 = in.tw[1];
+    if (!(in.limit >= 0.f)) bits |= CO_ST_MT_LIMIT_NEGATIVE;
+    for (int64_t c = 0; c < NC; ++c) {
+      const float s = in.tw[2 * c], e = in.tw[2 * c + 1];
+      const float d0 = tw_dist(in.lr[2 * c], in.lr[2 * c + 1], in.lr[0], in.lr[1]);
+      if (!(s >= 0.f) || !(e >= 0.f)) bits |= CO_ST_MT_TW_NEGATIVE;
+      if (!(in.svc[c] >= 0.f)) bits |= CO_ST_MT_SERVICE_NEGATIVE;
+      if (!(s < e)) bits |= CO_ST_MT_TW_INFEASIBLE;
+      if (!((s + d0) + in.svc[c] <= twe0)) bits |= CO_ST_MT_DEPOT_RETURN;
+    }
+    if (!range) {
+      const bool op = in.nopen == 0.0f;
+      float t = 0.f, len = 0.f, ul = 0.f, ub = 0.f;
+      int64_t prev = 0;
+      for (int64_t k = 0; k < T; ++k) {
+        const int64_t a = actions[b * sb + k * st];
+        const float d = tw_dist(in.lr[2 * prev], in.lr[2 * prev + 1], in.lr[2 * a],
+                                in.lr[2 * a + 1]);
+        len = len + d * ((op && a == 0) ? 0.0f : 1.0f);
+        if (!(len <= in.limit)) bits |= CO_ST_MT_ROUTE_LIMIT;
+        if (a == 0) len = 0.f;
+        t = tw_max(t + d, in.tw[2 * a]);
+        if (!(t <= in.tw[2 * a + 1])) bits |= CO_ST_MT_DEADLINE;
+        t = t + in.svc[a];
+        if (a == 0) t = 0.f;
+        const float m01 = a != 0 ? 1.0f : 0.0f;
+        ul = ul * m01 + in.dl[a];
+        ub = ub * m01 + in.db[a];
+        if (!(ul <= in.cap)) bits |= CO_ST_MT_OVER_LINEHAUL;
+        if (!(ub <= in.cap)) bits |= CO_ST_MT_OVER_BACKHAUL;
+        prev = a;
+      }
+    }
+    if (bits) set_status(status, bits);
+  }
+  return CO_OK;
+}
+
 CO_HOST_API const char* co_build_info(void) {
   return "rl4co_slap_amd co_env: host (CPU) build of the env / decode entry points";
 }
