@@ -1115,6 +1115,116 @@ int co_mtvrp_check(int64_t batch, int64_t num_loc, int64_t steps,
                    const co_mtvrp_instance* instance, const int64_t* actions,
                    int64_t act_stride_b, int64_t act_stride_t, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ PDP */
+
+/* The pickup-and-delivery problem (rl4co/envs/routing/pdp/env.py:20-234).  N = num_loc
+ * (even), h = N / 2, NC = N + 1 columns: column 0 is the depot, 1..h the pickups, h+1..N the
+ * deliveries; pickup p pairs with delivery p + h.  2 <= N <= CO_PDP_MAX_N and N even, else
+ * CO_E_INVAL from every entry, decided before the empty-batch return (an empty batch is a
+ * no-op); a NULL pointer not marked nullable is CO_E_INVAL.  available, to_deliver and
+ * action_mask are byte rows [B, NC]; a non-zero input byte counts as 1 and every output
+ * byte is 0 or 1.
+ *
+ * Reset (env.py:108-151):
+ *   locs[b]       = cat(depot[b], locs_in[b])            [NC, 2]
+ *   to_deliver[c] = c <= h        (h + 1 ones, then h zeros)
+ *   available[c]  = 1
+ *   action_mask[c] = c == 0       -- NOT available & to_deliver: the first step is the depot
+ *   current_node = i = 0 [B,1]; done = terminated = 0 [B,1]
+ *
+ * Step (env.py:67-106), a = action[b]:
+ *   pair = (a + h) % NC           (a pickup's delivery; the depot's pair is column h and a
+ *                                  delivery's a column 0..h-1, which reset left at 1 -- the
+ *                                  reference applies the rule to every action, so do we)
+ *   available[a] = 0 ; to_deliver[pair] = 1
+ *   action_mask  = available & to_deliver   -- from the two rows, never from the old mask
+ *   done = no column of available left ; reward = 0 (bool) ; i + 1 ; current_node = a
+ * An a outside 0..N sets CO_ST_INDEX_RANGE (torch's scatter raises) and edits neither row;
+ * i, current_node, done and the mask are written all the same.
+ *
+ * Reward (env.py:189-199) for actions [B, T]: minus the closed length of the tour
+ * [locs[0], locs[a_0], ..., locs[a_{T-1}]] over locs[b % locs_batch]: the T + 1 legs
+ * dist(p, q) = sqrtf(dx*dx + dy*dy) in f32 (every operation rounded on its own, as
+ * co_tsp_reward's), added in tour order in f64 from 0, the closing leg to the depot last,
+ * and rounded once: reward = -(float)sum.  A rollout from the depot has a zero first leg;
+ * one that starts at a pickup (multistart) visits the depot twice.  An a outside 0..N sets
+ * CO_ST_INDEX_RANGE and the legs that touch it are left out.
+ *
+ * Validity (env.py:201-216), check != 0, T odd (an even T with check is CO_E_INVAL: the
+ * reference's two slices then differ in length), T2 = T / 2, per row:
+ *   sort(actions) != arange(T): some value outside 0..T-1 or twice   CO_ST_PDP_NOT_ALL_NODES
+ *   else, pos = argsort(actions): !(pos[k] < pos[T2 + k]) for a k in 1..T2
+ *                                                                     CO_ST_PDP_PRECEDENCE
+ * On a permutation pos[k] < pos[T2 + k] says that value T2 + k appears after value k, which
+ * is tested when T2 + k is met in tour order.  A row that is not a permutation sets the
+ * first bit only (the reference's first assert ends the check). */
+#define CO_PDP_MAX_N 2046
+#define CO_ST_PDP_NOT_ALL_NODES 1048576  /* "Not visiting all nodes"       pdp/env.py:203-208 */
+#define CO_ST_PDP_PRECEDENCE 2097152     /* "Deliverying without pick-up"  pdp/env.py:210-216 */
+
+/* PDPEnv._reset (env.py:108-151) in one launch: every tensor stated above; depot [B,2],
+ * locs_in [B,N,2], locs_out [B,NC,2] (pairs: 8-byte aligned, else CO_E_ALIGN). */
+int co_pdp_reset(int64_t batch, int64_t num_loc, const float* depot, const float* locs_in,
+                 float* locs_out, uint8_t* available, uint8_t* to_deliver, uint8_t* action_mask,
+                 int64_t* current_node, int64_t* i, uint8_t* done, uint8_t* terminated,
+                 void* stream);
+
+/* PDPEnv._step (env.py:67-106) in one launch, out of place (the reference's scatter is):
+ * every output is a buffer of its own, though available_out / to_deliver_out may be their
+ * inputs (a lane reads the columns it writes).  i [B,1], current_out [B,1], done / reward
+ * [B].  One step moves 5 NC + 34 bytes per row (two byte rows in, three out; the action, i
+ * in and out, current_node, done and reward): 539 B at N = 100. */
+int co_pdp_step(int64_t batch, int64_t num_loc, const int64_t* action,
+                const uint8_t* available_in, const uint8_t* to_deliver_in,
+                uint8_t* available_out, uint8_t* to_deliver_out, uint8_t* action_mask,
+                const int64_t* i_in, int64_t* i_out, int64_t* current_out, uint8_t* done,
+                uint8_t* reward, int32_t* status, void* stream);
+
+/* `steps` (>= 1) preset co_pdp_step calls in one launch: action (t, b) at
+ * actions[t*act_stride_t + b*act_stride_b].  available / to_deliver / i / current_node are
+ * updated in place; action_mask (a buffer of its own), done and reward are written for the
+ * last step.  The final state is that of the `steps` single calls bit for bit.  feasible
+ * (nullable, u8 [steps, B]): the value action_mask[b, a_t] had before step t -- step 0 reads
+ * mask_in[b, a_0] (the caller's mask: after a reset it is not available & to_deliver), a
+ * later step tests available & to_deliver -- and 0 for an a_t outside 0..N.  On the device a
+ * row's two sets are bit words in registers for the whole call (32 columns per lane); per
+ * step the action is read and feasible written, the byte rows are stored once: 9 bytes
+ * per row-step plus 5 NC + 27 per row. */
+int co_pdp_steps(int64_t batch, int64_t num_loc, int64_t steps, const int64_t* actions,
+                 int64_t act_stride_t, int64_t act_stride_b, const uint8_t* mask_in,
+                 uint8_t* available, uint8_t* to_deliver, uint8_t* action_mask, int64_t* i,
+                 int64_t* current_node, uint8_t* done, uint8_t* reward, uint8_t* feasible,
+                 int32_t* status, void* stream);
+
+/* PDPEnv.get_reward for actions [B, T] (element (b, t) at b*act_stride_b + t*act_stride_t,
+ * 1 <= T <= 2048) on locs [locs_batch, NC, 2] (batch % locs_batch == 0; 8-byte aligned), and
+ * with check != 0 the two validity bits, in one pass over the row, as stated above. */
+int co_pdp_reward(int64_t batch, int64_t num_loc, int64_t steps, const float* locs,
+                  int64_t locs_batch, const int64_t* actions, int64_t act_stride_b,
+                  int64_t act_stride_t, int check, float* reward, int32_t* status,
+                  void* stream);
+
+/* co_decode_step fused with co_pdp_step for the selected action (the evaluated one in
+ * CO_DECODE_EVALUATE), device build only: logits [B, NC] (row stride logits_stride) and
+ * action_mask (the decode's mask) are read once, with available_in / to_deliver_in; the
+ * outputs are co_decode_step's (action_out, logp_sel, the status bits) and co_pdp_step's
+ * (available_out, to_deliver_out, mask_out = available & to_deliver, i_out, current_out,
+ * done, step_reward), the same bits as the two calls.  ll_accum (nullable) += logp_sel, as
+ * in co_tsp_decode_step.  mode: CO_DECODE_GREEDY / SAMPLING / EVALUATE with the FAST /
+ * CERTIFIED flags.  NC is odd, so the rows run on the byte-wise row engines.  mask_out may
+ * be action_mask (the mask edited in place): that call runs as the two launches and, like
+ * every two-launch route, refuses ll_accum (CO_E_INVAL).  A row-step
+ * reads 7 NC + 8 bytes (logits 4 NC, three byte rows, i) and writes 3 NC + 30 (three byte
+ * rows; action, logp, i, current_node, done, reward): 1,048 B at N = 100. */
+int co_pdp_decode_step(int64_t batch, int64_t num_loc, const float* logits,
+                       int64_t logits_stride, const uint8_t* action_mask, float tanh_clipping,
+                       float temperature, int mode, const int64_t* action_in,
+                       int64_t* action_out, float* logp_sel, uint64_t seed, uint64_t offset,
+                       const uint8_t* available_in, const uint8_t* to_deliver_in,
+                       uint8_t* available_out, uint8_t* to_deliver_out, uint8_t* mask_out,
+                       const int64_t* i_in, int64_t* i_out, int64_t* current_out, uint8_t* done,
+                       uint8_t* step_reward, float* ll_accum, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,12 @@ _SIGS = {
     "co_mtvrp_steps": [_i64, _i64, _i64, _p, _i64, _i64] + [_p] * 16,
     "co_mtvrp_reward": [_i64, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p],
     "co_mtvrp_check": [_i64, _i64, _i64, _p, _p, _i64, _i64, _p, _p],
+    "co_pdp_reset": [_i64, _i64] + [_p] * 11,
+    "co_pdp_step": [_i64, _i64] + [_p] * 13,
+    "co_pdp_steps": [_i64, _i64, _i64, _p, _i64, _i64] + [_p] * 11,
+    "co_pdp_reward": [_i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _p],
+    "co_pdp_decode_step": [_i64, _i64, _p, _i64, _p, _f32, _f32, _i32, _p, _p, _p, _u64, _u64]
+                          + [_p] * 13,
 }
 
 ST_INVALID_TOUR = 1
@@ -124,6 +130,9 @@ ST_TW_INFEASIBLE, ST_TW_DEADLINE = 512, 1024
 ST_MT_LIMIT_NEGATIVE, ST_MT_TW_NEGATIVE, ST_MT_SERVICE_NEGATIVE = 2048, 4096, 8192
 ST_MT_TW_INFEASIBLE, ST_MT_DEPOT_RETURN, ST_MT_ROUTE_LIMIT = 16384, 32768, 65536
 ST_MT_DEADLINE, ST_MT_OVER_LINEHAUL, ST_MT_OVER_BACKHAUL = 131072, 262144, 524288
+# CO_ST_PDP_*: co_pdp_reward's validity bits, one per message of the reference's check
+ST_PDP_NOT_ALL_NODES, ST_PDP_PRECEDENCE = 1048576, 2097152
+PDP_MAX_N = 2046  # CO_PDP_MAX_N: the largest (even) num_loc the PDP entries take
 MTVRP_MAX_N = 1023  # CO_MTVRP_MAX_N: the most customers the MTVRP entries take
 CVRPTW_MAX_N = 1023  # CO_CVRPTW_MAX_N: the most customers the CVRPTW entries take
 DT_F32, DT_I32, DT_I64 = 0, 1, 2  # CO_DT_*: dtype codes of durations / time_windows
@@ -207,6 +216,7 @@ HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt"
                 "co_cvrptw_steps",
                 "co_mtvrp_reset", "co_mtvrp_step", "co_mtvrp_action_mask", "co_mtvrp_steps",
                 "co_mtvrp_reward", "co_mtvrp_check",
+                "co_pdp_reset", "co_pdp_step", "co_pdp_steps", "co_pdp_reward",
                 "co_slap_reset", "co_slap_step", "co_slap_reward", "co_slap_local_search",
                 "co_gather_by_index", "co_best_of", "co_tsp_best_of",
                 "co_decode_step"]

@@ -1847,6 +1847,165 @@ CO_HOST_API int co_mtvrp_check(int64_t B, int64_t N, int64_t T, const co_mtvrp_i
   return CO_OK;
 }
 
+// ---------------------------------------------------------------------------- PDP
+// include/co_env.h (PDP): pdp/env.py:20-234, a plain loop per row.
+namespace {
+inline bool pdp_sizes_ok(int64_t B, int64_t N) {
+  return B >= 0 && N >= 2 && N <= CO_PDP_MAX_N && N % 2 == 0;
+}
+inline bool pdp_mis8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) != 0; }
+
+// one step on a row's two sets (env.py:67-89); false: the action is outside 0..N
+inline bool pdp_row_step(int64_t N, int64_t a, uint8_t* av, uint8_t* td) {
+  if (a < 0 || a > N) return false;
+  av[a] = 0;
+  td[(a + N / 2) % (N + 1)] = 1;
+  return true;
+}
+
+// mask = available & to_deliver on 0 / 1 bytes; -> a column of available is left
+inline bool pdp_row_mask(int64_t NC, uint8_t* av, uint8_t* td, uint8_t* mask) {
+  bool left = false;
+  for (int64_t c = 0; c < NC; ++c) {
+    av[c] = av[c] != 0;
+    td[c] = td[c] != 0;
+    mask[c] = av[c] & td[c];
+    left |= av[c] != 0;
+  }
+  return left;
+}
+}  // namespace
+
+// pdp/env.py:108-151
+CO_HOST_API int co_pdp_reset(int64_t B, int64_t N, const float* depot, const float* locs_in,
+                             float* locs_out, uint8_t* available, uint8_t* to_deliver,
+                             uint8_t* mask, int64_t* cur, int64_t* i, uint8_t* done,
+                             uint8_t* terminated, void*) {
+  if (!pdp_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!depot || !locs_in || !locs_out || !available || !to_deliver || !mask || !cur || !i ||
+      !done || !terminated)
+    return CO_E_INVAL;
+  if (pdp_mis8(depot) || pdp_mis8(locs_in) || pdp_mis8(locs_out)) return CO_E_ALIGN;
+  const int64_t NC = N + 1, h = N / 2;
+  for (int64_t b = 0; b < B; ++b) {
+    float* lo = locs_out + b * NC * 2;
+    lo[0] = depot[2 * b];
+    lo[1] = depot[2 * b + 1];
+    std::memcpy(lo + 2, locs_in + b * N * 2, (size_t)N * 2 * sizeof(float));
+    for (int64_t c = 0; c < NC; ++c) {
+      available[b * NC + c] = 1;
+      to_deliver[b * NC + c] = c <= h;
+      mask[b * NC + c] = c == 0;
+    }
+    cur[b] = 0;
+    i[b] = 0;
+    done[b] = 0;
+    terminated[b] = 0;
+  }
+  return CO_OK;
+}
+
+// pdp/env.py:67-106
+CO_HOST_API int co_pdp_step(int64_t B, int64_t N, const int64_t* action, const uint8_t* av_in,
+                            const uint8_t* td_in, uint8_t* av_out, uint8_t* td_out,
+                            uint8_t* mask, const int64_t* i_in, int64_t* i_out,
+                            int64_t* cur_out, uint8_t* done, uint8_t* reward, int32_t* status,
+                            void*) {
+  if (!pdp_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!action || !av_in || !td_in || !av_out || !td_out || !mask || !i_in || !i_out ||
+      !cur_out || !done || !reward)
+    return CO_E_INVAL;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b) {
+    uint8_t *av = av_out + b * NC, *td = td_out + b * NC;
+    if (av != av_in + b * NC) std::memcpy(av, av_in + b * NC, (size_t)NC);
+    if (td != td_in + b * NC) std::memcpy(td, td_in + b * NC, (size_t)NC);
+    if (!pdp_row_step(N, action[b], av, td)) set_status(status, CO_ST_INDEX_RANGE);
+    done[b] = !pdp_row_mask(NC, av, td, mask + b * NC);
+    reward[b] = 0;
+    i_out[b] = i_in[b] + 1;
+    cur_out[b] = action[b];
+  }
+  return CO_OK;
+}
+
+// `steps` co_pdp_step calls; feasible: the mask's value for a_t before step t
+CO_HOST_API int co_pdp_steps(int64_t B, int64_t N, int64_t T, const int64_t* actions,
+                             int64_t st, int64_t sb, const uint8_t* mask_in,
+                             uint8_t* available, uint8_t* to_deliver, uint8_t* mask, int64_t* i,
+                             int64_t* cur, uint8_t* done, uint8_t* reward, uint8_t* feasible,
+                             int32_t* status, void*) {
+  if (!pdp_sizes_ok(B, N) || T < 1 || T > (1 << 20)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!actions || !available || !to_deliver || !mask || !i || !cur || !done || !reward ||
+      (feasible && !mask_in) || mask == mask_in)
+    return CO_E_INVAL;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b) {
+    uint8_t *av = available + b * NC, *td = to_deliver + b * NC;
+    for (int64_t t = 0; t < T; ++t) {
+      const int64_t a = actions[t * st + b * sb];
+      const bool in = a >= 0 && a <= N;
+      if (feasible)
+        feasible[t * B + b] =
+            in && (t == 0 ? mask_in[b * NC + a] != 0 : (av[a] != 0 && td[a] != 0));
+      if (!pdp_row_step(N, a, av, td)) set_status(status, CO_ST_INDEX_RANGE);
+      cur[b] = a;
+    }
+    done[b] = !pdp_row_mask(NC, av, td, mask + b * NC);
+    reward[b] = 0;
+    i[b] += T;
+  }
+  return CO_OK;
+}
+
+// pdp/env.py:189-216: the reward and, with check, the two validity tests in tour order
+CO_HOST_API int co_pdp_reward(int64_t B, int64_t N, int64_t T, const float* locs, int64_t LB,
+                              const int64_t* actions, int64_t sb, int64_t st, int check,
+                              float* reward, int32_t* status, void*) {
+  if (!pdp_sizes_ok(B, N) || T < 1 || T > 2048 || (check && T % 2 == 0)) return CO_E_INVAL;
+  if (LB <= 0 || (B > 0 && B % LB != 0)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!locs || !actions || !reward || (check && !status)) return CO_E_INVAL;
+  if (pdp_mis8(locs)) return CO_E_ALIGN;
+  const int64_t NC = N + 1, T2 = T / 2;
+  std::vector<uint8_t> seen(check ? (size_t)T : 0);
+  for (int64_t b = 0; b < B; ++b) {
+    const float* lr = locs + (b % LB) * NC * 2;
+    bool dup = false, prec = false, have = true;
+    float px = lr[0], py = lr[1];
+    double len = 0.0;
+    if (check) std::fill(seen.begin(), seen.end(), 0);
+    for (int64_t t = 0; t < T; ++t) {
+      const int64_t a = actions[b * sb + t * st];
+      const bool in = a >= 0 && a <= N;
+      float qx = 0.f, qy = 0.f;
+      if (in) {
+        qx = lr[2 * a], qy = lr[2 * a + 1];
+        if (have) len += (double)edge_len(px, py, qx, qy);
+      } else {
+        set_status(status, CO_ST_INDEX_RANGE);
+      }
+      if (check) {
+        if (a < 0 || a >= T || seen[a]) {
+          dup = true;
+        } else {
+          if (a > T2 && !seen[a - T2]) prec = true;
+          seen[a] = 1;
+        }
+      }
+      px = qx, py = qy, have = in;
+    }
+    if (have) len += (double)edge_len(px, py, lr[0], lr[1]);
+    reward[b] = -(float)len;
+    if (check && dup) set_status(status, CO_ST_PDP_NOT_ALL_NODES);
+    if (check && !dup && prec) set_status(status, CO_ST_PDP_PRECEDENCE);
+  }
+  return CO_OK;
+}
+
 CO_HOST_API const char* co_build_info(void) {
   return "rl4co_slap_amd co_env: host (CPU) build of the env / decode entry points";
 }
