@@ -1225,6 +1225,163 @@ int co_pdp_decode_step(int64_t batch, int64_t num_loc, const float* logits,
                        const int64_t* i_in, int64_t* i_out, int64_t* current_out, uint8_t* done,
                        uint8_t* step_reward, float* ll_accum, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------- OP */
+
+/* The orienteering problem (rl4co/envs/routing/op/env.py:24-262, Kool et al.'s OP): collect
+ * prizes on a tour from and back to the depot whose length stays below max_length.  N =
+ * num_loc, NC = N + 1 columns, column 0 the depot.  1 <= N <= CO_OP_MAX_N, else CO_E_INVAL
+ * from every entry, decided before the empty-batch return (an empty batch is a no-op); a NULL
+ * pointer not marked nullable is CO_E_INVAL; locs hold pairs and must be 8-byte aligned
+ * (CO_E_ALIGN).  visited and action_mask are byte rows [B, NC]; a non-zero input byte counts
+ * as 1 and every output byte is 0 or 1.  CO_OP_MAX_N is bounded by the fused decode step,
+ * which keeps a lane's columns of locs and max_length in registers beside its logits: 16
+ * columns a lane on the 1,024-column row engine, the widest that does so without scratch.
+ *
+ * dist(p, q) is the CVRPTW section's sqrtf(dx*dx + dy*dy) in f32, every operation rounded on
+ * its own (no FMA); it is symmetric bit for bit.
+ *
+ * Reset (env.py:110-151):
+ *   locs[b]          = cat(depot[b], locs_in[b])                      [NC, 2]
+ *   prize[b]         = cat(0, prize_in[b])                            [NC]
+ *   max_length[b, c] = (max_length_in[b] - dist(depot[b], locs[b, c])) - 1e-6f   [NC], in
+ *                      f32, in that order: the length allowed on ARRIVAL at c
+ *   tour_length = current_total_prize = 0 [B] (f32); current_node = 0 [B,1]; i = 0 [B]
+ *   visited = 0 [B, NC], and the mask below on that state
+ *
+ * The mask (get_action_mask, env.py:153-169) of a state (visited, tour_length,
+ * current_node), c = 0..N:
+ *   cur        = locs[b, clamp(current_node, 0, N)]
+ *   exceeds[c] = tour_length + dist(locs[b, c], cur) > max_length[b, c]
+ *                -- one f32 add and one f32 compare, false for a NaN: a column with a NaN
+ *                coordinate (or a NaN tour_length) is never closed by the length test
+ *   mask[c]    = !(visited[c] | visited[0] | exceeds[c]);  mask[0] = 1 always
+ *
+ * The step (env.py:74-108), a = action[b]:
+ *   tour_length        += dist(locs[a], locs[clamp(current_node_in, 0, N)])
+ *   current_total_prize += prize[a]                                    (f32)
+ *   visited[a] = 1;  done = (a == 0) & (i_in > 0);  i + 1;  current_node = a
+ *   reward = 0 (bool, zeros_like(done)); then the mask above on the new state
+ * Two consequences of the reference's rule are kept:
+ *   - action 0 at i == 0 sets visited[0], so every customer closes; it does not set done;
+ *   - a row that is done goes on taking action 0 (the rollout pads with it): visited[0]
+ *     stays set, the leg is 0, and done stays 1.
+ * An a outside 0..N sets CO_ST_INDEX_RANGE (torch's scatter raises) and leaves visited,
+ * tour_length and current_total_prize unchanged; i + 1, current_node = a (so the next mask
+ * and leg take locs[clamp(a, 0, N)]), done by the rule above and the mask are written all
+ * the same -- the rule co_cvrptw_step and co_pdp_step state.
+ *
+ * Reward (env.py:171-180) for actions [B, T]: the sum of prize[b % prize_batch, a_t], added
+ * in tour order in f64 from 0 and rounded once.  An a_t outside 0..N sets CO_ST_INDEX_RANGE
+ * and adds nothing.  With T = 1 the reward is 0 and a non-zero action sets
+ * CO_ST_OP_SINGLE_NONZERO (the reference's assert).
+ *
+ * Validity (env.py:182-214), check != 0, per row:
+ *   a customer (1..N) met twice                                       CO_ST_OP_DUPLICATE
+ *   else len = the closed tour length of locs[a_0], ..., locs[a_{T-1}]: the T legs
+ *   dist(locs[a_t], locs[a_{t+1}]), the last one back to a_0, each in f32, added in tour
+ *   order in f64 from 0 and rounded once to f32 (legs that touch an a_t outside 0..N are
+ *   left out);
+ *   !(len <= (max_length[c] + dist(locs[0], locs[c]) + 1e-6f) + 1e-5f) for a column c, in
+ *   f32, left to right                                                CO_ST_OP_LENGTH
+ * A duplicate row sets the first bit alone (the reference's first assert ends the check). */
+#define CO_OP_MAX_N 1023
+#define CO_ST_OP_DUPLICATE 4194304        /* "Duplicates"                      op/env.py:194-197 */
+#define CO_ST_OP_LENGTH 8388608           /* "Max length exceeded by ..."      op/env.py:210-214 */
+#define CO_ST_OP_SINGLE_NONZERO 16777216  /* "If all length 1 tours, they should be zero" :175 */
+
+/* OPEnv._reset (env.py:110-151) in one launch: every tensor stated above.  depot [B,2],
+ * locs_in [B,N,2], prize_in [B,N], max_length_in [B]; locs_out [B,NC,2], prize_out and
+ * max_length_out [B,NC].  A row moves 12 N + 12 bytes in and 18 NC + 24 out. */
+int co_op_reset(int64_t batch, int64_t num_loc, const float* depot, const float* locs_in,
+                const float* prize_in, const float* max_length_in, float* locs_out,
+                float* prize_out, float* max_length_out, float* tour_length,
+                float* current_total_prize, int64_t* current_node, int64_t* i,
+                uint8_t* visited, uint8_t* action_mask, void* stream);
+
+/* OPEnv._step (env.py:74-108) in one launch, out of place: every output is a buffer of its
+ * own, though visited_out may be visited_in (a lane reads the columns it writes).  locs,
+ * prize and max_length are the post-reset [B,NC,..]; tour_length / current_total_prize / i
+ * / done / reward [B], current_node [B,1].  One step reads 13 NC + 52 bytes per row (locs 8
+ * NC, max_length 4 NC, visited NC; the action, two gathered locs, a prize, four scalars) and
+ * writes 2 NC + 26 (visited, the mask, five scalars, done, reward): 1,593 B at N = 100,
+ * against NC square roots. */
+int co_op_step(int64_t batch, int64_t num_loc, const int64_t* action, const float* locs,
+               const float* prize, const float* max_length, const uint8_t* visited_in,
+               uint8_t* visited_out, const float* tour_length_in, float* tour_length_out,
+               const float* total_prize_in, float* total_prize_out,
+               const int64_t* current_in, int64_t* current_out, const int64_t* i_in,
+               int64_t* i_out, uint8_t* done, uint8_t* reward, uint8_t* action_mask,
+               int32_t* status, void* stream);
+
+/* OPEnv.get_action_mask alone (env.py:153-169): 13 NC + 20 bytes read, NC written a row. */
+int co_op_action_mask(int64_t batch, int64_t num_loc, const float* locs,
+                      const float* max_length, const uint8_t* visited,
+                      const float* tour_length, const int64_t* current_node,
+                      uint8_t* action_mask, void* stream);
+
+/* `steps` (>= 1) preset co_op_step calls in one launch: action (t, b) at
+ * actions[t*act_stride_t + b*act_stride_b].  visited / tour_length / current_total_prize /
+ * current_node / i are updated in place; action_mask (a buffer of its own), done and reward
+ * are those of the last step.  The final state is that of the `steps` single calls bit for
+ * bit.  feasible (nullable, u8 [steps, B]): the value action_mask[b, a_t] had before step t
+ * -- step 0 reads mask_in[b, a_0] (the caller's mask), a later step evaluates the mask rule
+ * for column a_t alone -- and 0 for an a_t outside 0..N.  length (nullable, f32 [steps, B]):
+ * tour_length after step t.  On the device a row's visited set is bit words in registers
+ * for the whole call and the row scalars live on every lane of the row's group; a step
+ * reads the action, locs[a] and prize[a] (and max_length[a] for feasible): 20 bytes a
+ * row-step, 5 more written with feasible and length, plus 15 NC + 58 once per row. */
+int co_op_steps(int64_t batch, int64_t num_loc, int64_t steps, const int64_t* actions,
+                int64_t act_stride_t, int64_t act_stride_b, const float* locs,
+                const float* prize, const float* max_length, const uint8_t* mask_in,
+                uint8_t* visited, float* tour_length, float* current_total_prize,
+                int64_t* current_node, int64_t* i, uint8_t* done, uint8_t* reward,
+                uint8_t* action_mask, uint8_t* feasible, float* length, int32_t* status,
+                void* stream);
+
+/* OPEnv.get_reward for actions [B, T] (element (b, t) at b*act_stride_b + t*act_stride_t,
+ * 1 <= T <= 2^20) on prize [prize_batch, NC] (batch % prize_batch == 0) and, with check !=
+ * 0, the validity bits on locs [locs_batch, NC, 2] and max_length [locs_batch, NC] (batch %
+ * locs_batch == 0; both may be NULL without check), in one pass over the row, as stated
+ * above: 12 bytes a tour step (20 with check) and 16 NC a row for the length test. */
+int co_op_reward(int64_t batch, int64_t num_loc, int64_t steps, const float* prize,
+                 int64_t prize_batch, const float* locs, const float* max_length,
+                 int64_t locs_batch, const int64_t* actions, int64_t act_stride_b,
+                 int64_t act_stride_t, int check, float* reward, int32_t* status,
+                 void* stream);
+
+/* The post-reset instance tensors of OP, one pointer each, handed to co_op_decode_step as one
+ * table in host memory (the entry's arguments stay within the 28 integer-class slots every
+ * entry of this header keeps to); it is read during the call and need not outlive it.  A
+ * NULL table or member is CO_E_INVAL. */
+typedef struct co_op_instance {
+  const float* locs;       /* [B, NC, 2], 8-byte aligned */
+  const float* prize;      /* [B, NC] */
+  const float* max_length; /* [B, NC] */
+} co_op_instance;
+
+/* co_decode_step fused with co_op_step for the selected action (the evaluated one in
+ * CO_DECODE_EVALUATE), device build only: logits [B, NC] (row stride logits_stride) and
+ * action_mask (the decode's mask) are read once, with the row's visited, locs and
+ * max_length; the outputs are co_decode_step's (action_out, logp_sel, the status bits) and
+ * co_op_step's, the same bits as the two calls.  ll_accum (nullable) += logp_sel, as in
+ * co_tsp_decode_step.  mode: CO_DECODE_GREEDY / SAMPLING / EVALUATE with the FAST /
+ * CERTIFIED flags.  Every output is a buffer of its own; mask_out may be action_mask (the
+ * mask edited in place): that call runs as the two launches and, like every two-launch
+ * route, refuses ll_accum (CO_E_INVAL).  A row-step reads 18 NC + 44 bytes (logits 4 NC, two
+ * byte rows, locs 8 NC, max_length 4 NC, the scalars and gathers of co_op_step less the
+ * action) and writes 2 NC + 38: 2,102 B at N = 100, against 2,110 B for the two calls -- the fused step
+ * saves a launch, not traffic. */
+int co_op_decode_step(int64_t batch, int64_t num_loc, const float* logits,
+                      int64_t logits_stride, const uint8_t* action_mask, float tanh_clipping,
+                      float temperature, int mode, const int64_t* action_in,
+                      int64_t* action_out, float* logp_sel, uint64_t seed, uint64_t offset,
+                      const co_op_instance* instance, const uint8_t* visited_in,
+                      uint8_t* visited_out, const float* tour_length_in, float* tour_length_out,
+                      const float* total_prize_in, float* total_prize_out,
+                      const int64_t* current_in, int64_t* current_out, const int64_t* i_in,
+                      int64_t* i_out, uint8_t* done, uint8_t* step_reward, uint8_t* mask_out,
+                      float* ll_accum, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

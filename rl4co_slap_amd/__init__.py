@@ -8,9 +8,9 @@ and ``rl4co.envs`` registry names.
 """
 from . import _native
 from .envs import (ENV_REGISTRY, IMPROVEMENT_ENV_REGISTRY, MULTITASK_ENV_REGISTRY,
-                   PICKUP_DELIVERY_ENV_REGISTRY, ROUTING_VARIANT_ENV_REGISTRY, CVRPEnv,
+                   ORIENTEERING_ENV_REGISTRY, PICKUP_DELIVERY_ENV_REGISTRY, ROUTING_VARIANT_ENV_REGISTRY, CVRPEnv,
                    CVRPTWEnv, CVRPTWGenerator, ImprovementEnvBase, MTVRPEnv, MTVRPGenerator,
-                   PDPEnv, PDPGenerator, SLAPEnv, TSPEnv, TSPkoptEnv, get_env)
+                   OPEnv, OPGenerator, PDPEnv, PDPGenerator, SLAPEnv, TSPEnv, TSPkoptEnv, get_env)
 from .td import TensorDict
 from .tasks import (AugmentationEval, EvalBase, GreedyEval, GreedyMultiStartAugmentEval,
                     GreedyMultiStartEval, SamplingEval, evaluate_policy,
@@ -37,4 +37,5 @@ __all__ = ["ENV_REGISTRY", "CVRPEnv", "SLAPEnv", "TSPEnv", "get_env", "TensorDic
            "evaluate_policy", "get_automatic_batch_size", "TSPkoptEnv", "ImprovementEnvBase",
            "IMPROVEMENT_ENV_REGISTRY", "CVRPTWEnv", "CVRPTWGenerator",
            "ROUTING_VARIANT_ENV_REGISTRY", "MTVRPEnv", "MTVRPGenerator",
-           "MULTITASK_ENV_REGISTRY", "PDPEnv", "PDPGenerator", "PICKUP_DELIVERY_ENV_REGISTRY"]
+           "MULTITASK_ENV_REGISTRY", "PDPEnv", "PDPGenerator", "PICKUP_DELIVERY_ENV_REGISTRY",
+           "OPEnv", "OPGenerator", "ORIENTEERING_ENV_REGISTRY"]

@@ -115,6 +115,15 @@ _SIGS = {
     "co_pdp_reward": [_i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _p],
     "co_pdp_decode_step": [_i64, _i64, _p, _i64, _p, _f32, _f32, _i32, _p, _p, _p, _u64, _u64]
                           + [_p] * 13,
+    "co_op_reset": [_i64, _i64] + [_p] * 14,
+    "co_op_step": [_i64, _i64] + [_p] * 19,
+    "co_op_action_mask": [_i64, _i64] + [_p] * 7,
+    "co_op_steps": [_i64, _i64, _i64, _p, _i64, _i64] + [_p] * 16,
+    "co_op_reward": [_i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i32, _p, _p,
+                     _p],
+    # the co_op_instance table (op_instance below) is one pointer argument
+    "co_op_decode_step": [_i64, _i64, _p, _i64, _p, _f32, _f32, _i32, _p, _p, _p, _u64, _u64]
+                         + [_p] * 17,
 }
 
 ST_INVALID_TOUR = 1
@@ -132,6 +141,9 @@ ST_MT_TW_INFEASIBLE, ST_MT_DEPOT_RETURN, ST_MT_ROUTE_LIMIT = 16384, 32768, 65536
 ST_MT_DEADLINE, ST_MT_OVER_LINEHAUL, ST_MT_OVER_BACKHAUL = 131072, 262144, 524288
 # CO_ST_PDP_*: co_pdp_reward's validity bits, one per message of the reference's check
 ST_PDP_NOT_ALL_NODES, ST_PDP_PRECEDENCE = 1048576, 2097152
+# CO_ST_OP_*: co_op_reward's bits, one per message of the reference's two checks and assert
+ST_OP_DUPLICATE, ST_OP_LENGTH, ST_OP_SINGLE_NONZERO = 4194304, 8388608, 16777216
+OP_MAX_N = 1023  # CO_OP_MAX_N: the most customers the OP entries take
 PDP_MAX_N = 2046  # CO_PDP_MAX_N: the largest (even) num_loc the PDP entries take
 MTVRP_MAX_N = 1023  # CO_MTVRP_MAX_N: the most customers the MTVRP entries take
 CVRPTW_MAX_N = 1023  # CO_CVRPTW_MAX_N: the most customers the CVRPTW entries take
@@ -217,6 +229,7 @@ HOST_SYMBOLS = ["co_tsp_reset", "co_tsp_step", "co_tsp_reward", "co_tsp_two_opt"
                 "co_mtvrp_reset", "co_mtvrp_step", "co_mtvrp_action_mask", "co_mtvrp_steps",
                 "co_mtvrp_reward", "co_mtvrp_check",
                 "co_pdp_reset", "co_pdp_step", "co_pdp_steps", "co_pdp_reward",
+                "co_op_reset", "co_op_step", "co_op_action_mask", "co_op_steps", "co_op_reward",
                 "co_slap_reset", "co_slap_step", "co_slap_reward", "co_slap_local_search",
                 "co_gather_by_index", "co_best_of", "co_tsp_best_of",
                 "co_decode_step"]
@@ -301,6 +314,22 @@ def mtvrp_instance(*tensors) -> MtvrpInstance:
     NULL member)."""
     assert len(tensors) == len(MtvrpInstance.FIELDS)
     return MtvrpInstance(*(ptr(t) for t in tensors))
+
+
+class OpInstance(ctypes.Structure):
+    """``co_op_instance`` (include/co_env.h): OP's post-reset instance pointers as one table."""
+    FIELDS = ("locs", "prize", "max_length")
+    _fields_ = [(name, ctypes.c_void_p) for name in FIELDS]
+
+    @property
+    def address(self) -> int:
+        """What a call passes; the table must stay referenced until the call returns."""
+        return ctypes.addressof(self)
+
+
+def op_instance(locs, prize, max_length) -> OpInstance:
+    """The table of the three instance tensors."""
+    return OpInstance(ptr(locs), ptr(prize), ptr(max_length))
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)

@@ -21,7 +21,8 @@ SOURCES = ["tsp.hip", "cvrp.hip", "slap.hip", "ops.hip", "decode_step.hip", "dec
            "decode_env.hip",
            "rollout.hip",
            "nearest.hip", "tsp_ls.hip", "cvrp_ls.hip", "slap_ls.hip", "best_of.hip",
-           "tsp_kopt.hip", "cvrptw.hip", "mtvrp.hip", "pdp.hip", "decode_pdp.hip"]
+           "tsp_kopt.hip", "cvrptw.hip", "mtvrp.hip", "pdp.hip", "decode_pdp.hip", "op.hip",
+           "decode_op.hip"]
 HEADERS = ["co_common.hpp", "co_tile.hpp", "co_math.hpp", "co_diag.hpp", "decode_common.hpp",
            "decode_fused.hpp", "co_local_search.hpp"]
 ARCH = "gfx950"

@@ -2006,6 +2006,220 @@ CO_HOST_API int co_pdp_reward(int64_t B, int64_t N, int64_t T, const float* locs
   return CO_OK;
 }
 
+// ----------------------------------------------------------------------------- OP
+// include/co_env.h (OP): op/env.py:24-262, a plain loop per row.
+namespace {
+inline bool op_sizes_ok(int64_t B, int64_t N) { return B >= 0 && N >= 1 && N <= CO_OP_MAX_N; }
+inline bool op_mis8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) != 0; }
+inline int64_t op_clamp(int64_t a, int64_t N) { return a < 0 ? 0 : (a > N ? N : a); }
+
+// env.py:153-169 for one column of a row's state; cl = locs[clamp(current_node)]
+inline bool op_open(const float* lr, const float* ml, const uint8_t* vis, float tl,
+                    const float* cl, int64_t c) {
+  if (c == 0) return true;
+  const bool exceeds = tl + edge_len(lr[2 * c], lr[2 * c + 1], cl[0], cl[1]) > ml[c];
+  return !(vis[c] != 0 || vis[0] != 0 || exceeds);
+}
+
+inline void op_row_mask(int64_t NC, const float* lr, const float* ml, const uint8_t* vis,
+                        float tl, int64_t cur, uint8_t* mask) {
+  const float* cl = lr + 2 * op_clamp(cur, NC - 1);
+  for (int64_t c = 0; c < NC; ++c) mask[c] = op_open(lr, ml, vis, tl, cl, c);
+}
+
+// env.py:74-108 on a row's state (vis holds 0 / 1 bytes); false: a is outside 0..N
+inline bool op_row_step(int64_t N, int64_t a, const float* lr, const float* pr, uint8_t* vis,
+                        float& tl, float& pz, int64_t& cur, int64_t& i, uint8_t& done) {
+  const bool in = a >= 0 && a <= N;
+  if (in) {
+    const float* cl = lr + 2 * op_clamp(cur, N);
+    tl = tl + edge_len(lr[2 * a], lr[2 * a + 1], cl[0], cl[1]);
+    pz = pz + pr[a];
+    vis[a] = 1;
+  }
+  done = a == 0 && i > 0;
+  i += 1;
+  cur = a;
+  return in;
+}
+}  // namespace
+
+// op/env.py:110-151
+CO_HOST_API int co_op_reset(int64_t B, int64_t N, const float* depot, const float* locs_in,
+                            const float* prize_in, const float* max_length_in, float* locs_out,
+                            float* prize_out, float* max_length_out, float* tour_length,
+                            float* total_prize, int64_t* cur, int64_t* i, uint8_t* visited,
+                            uint8_t* mask, void*) {
+  if (!op_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!depot || !locs_in || !prize_in || !max_length_in || !locs_out || !prize_out ||
+      !max_length_out || !tour_length || !total_prize || !cur || !i || !visited || !mask)
+    return CO_E_INVAL;
+  if (op_mis8(depot) || op_mis8(locs_in) || op_mis8(locs_out)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b) {
+    float *lo = locs_out + b * NC * 2, *po = prize_out + b * NC, *mo = max_length_out + b * NC;
+    lo[0] = depot[2 * b];
+    lo[1] = depot[2 * b + 1];
+    std::memcpy(lo + 2, locs_in + b * N * 2, (size_t)N * 2 * sizeof(float));
+    po[0] = 0.f;
+    std::memcpy(po + 1, prize_in + b * N, (size_t)N * sizeof(float));
+    for (int64_t c = 0; c < NC; ++c) {
+      mo[c] = (max_length_in[b] - edge_len(lo[0], lo[1], lo[2 * c], lo[2 * c + 1])) - 1e-6f;
+      visited[b * NC + c] = 0;
+    }
+    tour_length[b] = 0.f;
+    total_prize[b] = 0.f;
+    cur[b] = 0;
+    i[b] = 0;
+    op_row_mask(NC, lo, mo, visited + b * NC, 0.f, 0, mask + b * NC);
+  }
+  return CO_OK;
+}
+
+// op/env.py:74-108
+CO_HOST_API int co_op_step(int64_t B, int64_t N, const int64_t* action, const float* locs,
+                           const float* prize, const float* max_length,
+                           const uint8_t* visited_in, uint8_t* visited_out, const float* tl_in,
+                           float* tl_out, const float* pz_in, float* pz_out,
+                           const int64_t* cur_in, int64_t* cur_out, const int64_t* i_in,
+                           int64_t* i_out, uint8_t* done, uint8_t* reward, uint8_t* mask,
+                           int32_t* status, void*) {
+  if (!op_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!action || !locs || !prize || !max_length || !visited_in || !visited_out || !tl_in ||
+      !tl_out || !pz_in || !pz_out || !cur_in || !cur_out || !i_in || !i_out || !done ||
+      !reward || !mask)
+    return CO_E_INVAL;
+  if (op_mis8(locs)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b) {
+    const float* lr = locs + b * NC * 2;
+    uint8_t* vis = visited_out + b * NC;
+    for (int64_t c = 0; c < NC; ++c) vis[c] = visited_in[b * NC + c] != 0;
+    float tl = tl_in[b], pz = pz_in[b];
+    int64_t cur = cur_in[b], iv = i_in[b];
+    if (!op_row_step(N, action[b], lr, prize + b * NC, vis, tl, pz, cur, iv, done[b]))
+      set_status(status, CO_ST_INDEX_RANGE);
+    tl_out[b] = tl, pz_out[b] = pz, cur_out[b] = cur, i_out[b] = iv;
+    reward[b] = 0;
+    op_row_mask(NC, lr, max_length + b * NC, vis, tl, cur, mask + b * NC);
+  }
+  return CO_OK;
+}
+
+// op/env.py:153-169
+CO_HOST_API int co_op_action_mask(int64_t B, int64_t N, const float* locs,
+                                  const float* max_length, const uint8_t* visited,
+                                  const float* tour_length, const int64_t* cur, uint8_t* mask,
+                                  void*) {
+  if (!op_sizes_ok(B, N)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!locs || !max_length || !visited || !tour_length || !cur || !mask) return CO_E_INVAL;
+  if (op_mis8(locs)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b)
+    op_row_mask(NC, locs + b * NC * 2, max_length + b * NC, visited + b * NC, tour_length[b],
+                cur[b], mask + b * NC);
+  return CO_OK;
+}
+
+// `steps` co_op_step calls; feasible: the mask's value for a_t before step t
+CO_HOST_API int co_op_steps(int64_t B, int64_t N, int64_t T, const int64_t* actions, int64_t st,
+                            int64_t sb, const float* locs, const float* prize,
+                            const float* max_length, const uint8_t* mask_in, uint8_t* visited,
+                            float* tour_length, float* total_prize, int64_t* cur, int64_t* i,
+                            uint8_t* done, uint8_t* reward, uint8_t* mask, uint8_t* feasible,
+                            float* length, int32_t* status, void*) {
+  if (!op_sizes_ok(B, N) || T < 1 || T > (1 << 20)) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!actions || !locs || !prize || !max_length || !visited || !tour_length || !total_prize ||
+      !cur || !i || !done || !reward || !mask || (feasible && !mask_in) || mask == mask_in)
+    return CO_E_INVAL;
+  if (op_mis8(locs)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  for (int64_t b = 0; b < B; ++b) {
+    const float *lr = locs + b * NC * 2, *ml = max_length + b * NC;
+    uint8_t* vis = visited + b * NC;
+    for (int64_t c = 0; c < NC; ++c) vis[c] = vis[c] != 0;
+    for (int64_t t = 0; t < T; ++t) {
+      const int64_t a = actions[t * st + b * sb];
+      const bool in = a >= 0 && a <= N;
+      if (feasible)
+        feasible[t * B + b] =
+            in && (t == 0 ? mask_in[b * NC + a] != 0
+                          : op_open(lr, ml, vis, tour_length[b], lr + 2 * op_clamp(cur[b], N), a));
+      if (!op_row_step(N, a, lr, prize + b * NC, vis, tour_length[b], total_prize[b], cur[b],
+                       i[b], done[b]))
+        set_status(status, CO_ST_INDEX_RANGE);
+      if (length) length[t * B + b] = tour_length[b];
+    }
+    reward[b] = 0;
+    op_row_mask(NC, lr, ml, vis, tour_length[b], cur[b], mask + b * NC);
+  }
+  return CO_OK;
+}
+
+// op/env.py:171-214: the prize sum and, with check, the two validity tests in tour order
+CO_HOST_API int co_op_reward(int64_t B, int64_t N, int64_t T, const float* prize, int64_t PB,
+                             const float* locs, const float* max_length, int64_t LB,
+                             const int64_t* actions, int64_t sb, int64_t st, int check,
+                             float* reward, int32_t* status, void*) {
+  if (!op_sizes_ok(B, N) || T < 1 || T > (1 << 20)) return CO_E_INVAL;
+  if (PB <= 0 || (B > 0 && B % PB != 0)) return CO_E_INVAL;
+  if (check && (LB <= 0 || (B > 0 && B % LB != 0))) return CO_E_INVAL;
+  if (B == 0) return CO_OK;
+  if (!prize || !actions || !reward || (check && (!locs || !max_length || !status)))
+    return CO_E_INVAL;
+  if (check && op_mis8(locs)) return CO_E_ALIGN;
+  const int64_t NC = N + 1;
+  std::vector<uint8_t> seen(check ? (size_t)NC : 0);
+  for (int64_t b = 0; b < B; ++b) {
+    const float* pr = prize + (b % PB) * NC;
+    const float* lr = check ? locs + (b % LB) * NC * 2 : nullptr;
+    bool dup = false, have = false, have0 = false;
+    float px = 0.f, py = 0.f, fx = 0.f, fy = 0.f;
+    double sum = 0.0, len = 0.0;
+    if (check) std::fill(seen.begin(), seen.end(), 0);
+    for (int64_t t = 0; t < T; ++t) {
+      const int64_t a = actions[b * sb + t * st];
+      const bool in = a >= 0 && a <= N;
+      if (in)
+        sum += (double)pr[a];
+      else
+        set_status(status, CO_ST_INDEX_RANGE);
+      if (check) {
+        float qx = 0.f, qy = 0.f;
+        if (in) {
+          qx = lr[2 * a], qy = lr[2 * a + 1];
+          if (have) len += (double)edge_len(px, py, qx, qy);
+          if (a != 0 && seen[a]) dup = true;
+          seen[a] = 1;
+        }
+        if (t == 0) fx = qx, fy = qy, have0 = in;
+        px = qx, py = qy, have = in;
+      }
+    }
+    reward[b] = T == 1 ? 0.f : (float)sum;
+    if (T == 1 && actions[b * sb] != 0) set_status(status, CO_ST_OP_SINGLE_NONZERO);
+    if (!check) continue;
+    if (dup) {
+      set_status(status, CO_ST_OP_DUPLICATE);
+      continue;
+    }
+    if (have && have0) len += (double)edge_len(px, py, fx, fy);
+    const float flen = (float)len;
+    const float* ml = max_length + (b % LB) * NC;
+    bool over = false;
+    for (int64_t c = 0; c < NC; ++c) {
+      const float bound = ((ml[c] + edge_len(lr[0], lr[1], lr[2 * c], lr[2 * c + 1])) + 1e-6f) + 1e-5f;
+      over |= !(flen <= bound);
+    }
+    if (over) set_status(status, CO_ST_OP_LENGTH);
+  }
+  return CO_OK;
+}
+
 CO_HOST_API const char* co_build_info(void) {
   return "rl4co_slap_amd co_env: host (CPU) build of the env / decode entry points";
 }
